@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: training pairs/s of the two-tower step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload northstar|config2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload northstar|config2] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 Workload (default = BASELINE.json north star): synthetic 100M-item x 50M-user two-tower, emb_dim
@@ -19,8 +19,13 @@ call), relays its output and exits with its status; under a launcher the world s
 --gpus. Timing: W untimed steps, synchronize + barrier, K timed steps, synchronize (each rank's clock
 read here) + barrier, max over ranks (the closing barrier's collective outside the interval, its
 inclusive figure reported beside: end_timed_region); rank 0 prints ONE JSON line.
-Also reported: the embedding path's dominant kernel against the HBM roofline (HIP events on its
-own stream) and the CPU restatement's pairs/s on this host (rank 0, N = 1, bounded sample).
+A plain run does only that: set up, warm up, time the K steps, print the line (``roofline`` and
+``cpu_baseline`` null at N = 1). ``--full`` also reports the embedding path's dominant kernel against
+the HBM roofline (per-launch device times from an instrumented replay of their own), the CPU
+restatement's pairs/s on this host (rank 0, N = 1, bounded sample) and, with ``--path dropin``, the
+generic per-op path beside the fused one. ``--dump-outputs DIR`` writes what the last timed step
+computed as ``DIR/<name>.npy`` (dump_outputs below); the inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -72,7 +77,14 @@ def parse():
     ap.add_argument("--workload", default="northstar", choices=sorted(WORKLOADS) + sorted(SHARDED))
     ap.add_argument("--ids", default=None, choices=["uniform", "zipf"],
                     help="id distribution (default uniform; config4: zipf)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline figure does not need: per-launch "
+                         "device times and the roofline report (instrumented or eager runs of their own), the CPU "
+                         "baseline (unless --no-cpu-baseline), the drop-in path's generic-path comparison")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed (loss, logits, tower "
+                         "parameters, a fixed sample of table rows and their Adagrad state) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-rows", type=int, default=0,
                     help="table rows of the CPU sample (0: the workload's full tables when host RAM allows)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline: timed seconds of steps")
@@ -445,6 +457,39 @@ def end_timed_region(t0: float, dev) -> tuple:
     return float(dt[0]), float(dt[1])
 
 
+DUMP_ROWS = 4096  # table rows per sample of --dump-outputs (2 samples x 2 tables x 4096 x D fp32: 8 MB at D = 128)
+
+
+def dump_outputs(out_dir, step, ids=None):
+    """--dump-outputs: what the last timed step left with the caller, as ``out_dir/<name>.npy`` (fp32):
+    loss, logits, pooled rows and the flat tower parameters where the step has them, and of every
+    table (a FusedTwoTowerStep's) two fixed row samples with their row-wise Adagrad state: the first
+    DUMP_ROWS ids of the first resident batch (rows the run has trained) and DUMP_ROWS rows drawn
+    with a fixed seed (mostly rows as initialised). The inputs are seeded, so two builds run with
+    the same arguments write comparable files."""
+    os.makedirs(out_dir, exist_ok=True)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    arrays = {}
+    for name in ("loss", "logits", "params"):
+        t = getattr(step, name, None)
+        if isinstance(t, torch.Tensor):
+            arrays[name] = t.detach().reshape(-1)
+    if getattr(step, "materialize_pooled", False):  # else the pooled rows stay on chip
+        arrays["pooled"] = step.pooled
+    tables = getattr(step, "tables", None)
+    if tables is not None and hasattr(tables, "table_view"):
+        g = torch.Generator().manual_seed(12345)
+        for t, n in enumerate(tables.rows[:len(ids) if ids is not None else 0]):
+            picks = {"batch0": (ids[t].reshape(-1)[:DUMP_ROWS].to(torch.int64) % n),
+                     "seeded": torch.randint(0, n, (DUMP_ROWS,), generator=g).to(tables.device)}
+            for how, rows in picks.items():
+                arrays[f"table{t}_{how}_rows"] = tables.table_view(t)[rows]
+                arrays[f"table{t}_{how}_state"] = tables.state_view(t)[rows]
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def run_multihot(args):
     """SURVEY 8(d) config 5 shape at N = 1: the fused step on multi-hot KJT input (tt_pooled_fwd ->
     fused towers T1 -> tiled tt_bwd_prepare (side stream) -> T2/T3 (side stream) ->
@@ -480,6 +525,11 @@ def run_multihot(args):
     ms = dt / args.steps * 1e3
     value = args.steps * B / dt
     loss = float(step.loss)
+    if args.dump_outputs:
+        nb0 = int(batches[0][1][B])
+        dump_outputs(args.dump_outputs, step, [batches[0][0][:nb0], batches[0][0][nb0:]])
+    if not args.full:
+        return value, ms, loss, None, None, args.steps
     # per-launch device time: eager steps with HIP events around each launch on its stream
     step._timing = []
     try:
@@ -606,6 +656,8 @@ def run_multi_kjt(args, world, rank, local_rank):
     dt, dt_barrier = end_timed_region(t0, dev)
     step.check()
     loss = float(step.loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step)
     step.release_graphs()
     if peer:
         dist.barrier()  # no rank unmaps a peer's buffer while that peer may still store into it
@@ -744,6 +796,10 @@ def run_single(args):
     ms = dt / steps_run * 1e3
     value = steps_run * B / dt
     loss = float(step.loss)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step, batches[0][0])
+    if not args.full:
+        return value, ms, loss, None, None, steps_run
     # ---- per-launch device time inside the replayed graphs: the same graphs re-captured with
     # event-record nodes around every kernel node (graph_timing.py), replayed for K steps;
     # eager steps with HIP events around each launch if the graph cannot be instrumented
@@ -879,17 +935,21 @@ def run_dropin(args, world=1, rank=0, local_rank=0):
             "generic_steps": fd.steps_generic if fd else args.warmup + args.steps,
             "loop": "DistributedModelParallel + TrainPipelineSparseDist.progress + KeyedOptimizerWrapper(Adam) + "
                     "RowWiseAdagrad in backward (03_model_training.py:612-625, :770-829); resident device KJTs"}
-    # the same loop with the dispatch off: the generic per-op path (pooled fwd, per-layer GEMMs, dot +
-    # BCE, autograd, dedup + Adagrad kernels, torch Adam) on the same storage
-    os.environ["TT_DROPIN_FUSED"] = "0"
-    try:
-        gp = TrainPipelineSparseDist(model, optimizer, dev)
-        gsteps = min(args.steps, 20)
-        gdt, _ = timed(gp, 3, gsteps)
-    finally:
-        os.environ.pop("TT_DROPIN_FUSED", None)
-    info["generic_path"] = {"ms_per_step": round(gdt / gsteps * 1e3, 4), "pairs/s": round(world * gsteps * B / gdt, 1),
-                            "steps": gsteps}
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "loss.npy"), np.asarray([loss], np.float32))
+    if args.full:
+        # the same loop with the dispatch off: the generic per-op path (pooled fwd, per-layer GEMMs, dot +
+        # BCE, autograd, dedup + Adagrad kernels, torch Adam) on the same storage
+        os.environ["TT_DROPIN_FUSED"] = "0"
+        try:
+            gp = TrainPipelineSparseDist(model, optimizer, dev)
+            gsteps = min(args.steps, 20)
+            gdt, _ = timed(gp, 3, gsteps)
+        finally:
+            os.environ.pop("TT_DROPIN_FUSED", None)
+        info["generic_path"] = {"ms_per_step": round(gdt / gsteps * 1e3, 4),
+                                "pairs/s": round(world * gsteps * B / gdt, 1), "steps": gsteps}
     if world > 1 and fd:
         st = fd.step
         info["sharded"] = {"sharding": fd.sharding, "owners": fd.owners, "step": fd.mode,
@@ -927,6 +987,8 @@ def run_host_fed(args):
     n = pipe.run(src, max_steps=steps)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step, [torch.from_numpy(np.asarray(c)).to(dev) for c in host[0][0]])
     info = pipe.summary()
     info.update(graphs="production ring" if pipe.ring else "classic pool", steps_per_group=g,
                 host_cpus=len(os.sched_getaffinity(0)), torch_threads=torch.get_num_threads())
@@ -987,6 +1049,8 @@ def run_multi(args, world, rank, local_rank):
     dt, dt_barrier = end_timed_region(t0, dev)
     step.check()
     loss = float(step.loss)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step)
     step.release_graphs()  # before the process group is destroyed
     r = step.rank
     if peer:

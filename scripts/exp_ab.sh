@@ -19,7 +19,7 @@ PY
 for i in 1 2 3; do
   for v in ${ORDER:-prev new}; do
     if [ $v = prev ] || [ "${AA:-0}" = 1 ]; then L="TT_EXPERIMENT_LIB=$PWD/two_tower_recommender_model_amd/lib_prev/libtt_mi355x.so"; else L=""; fi
-    env $L timeout -k 10 200 python bench.py --no-cpu-baseline --steps 100 --warmup 20 ${BENCH_ARGS:-} > $O/${v}_$i.log 2>&1 || exit $?
+    env $L timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 100 --warmup 20 ${BENCH_ARGS:-} > $O/${v}_$i.log 2>&1 || exit $?
     summ $O/${v}_$i.log $v || exit $?
   done
 done

@@ -19,7 +19,7 @@ for i in $(seq 1 ${R:-3}); do
       *) L="TT_EXPERIMENT_LIB=$P/lib_var/$lib/libtt_mi355x.so" ;;
     esac
     L="$L $extra"
-    env $L timeout -k 10 200 python bench.py --no-cpu-baseline --steps 100 --warmup 20 ${BENCH_ARGS:-} > "$O/${v//[+=]/_}_$i.log" 2>&1 || exit $?
+    env $L timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 100 --warmup 20 ${BENCH_ARGS:-} > "$O/${v//[+=]/_}_$i.log" 2>&1 || exit $?
     python - "$O/${v//[+=]/_}_$i.log" $v <<'PY' || exit $?
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

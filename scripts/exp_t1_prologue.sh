@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 O=gpurun_out/exp_t1p
 mkdir -p $O
 for d in 0 16 32 48 0; do
-  TT_EXPERIMENT_LIB=1 TT_T1_DEBUG=$d timeout -k 10 200 python bench.py --no-cpu-baseline --steps 100 --warmup 20 > $O/bench_$d.log 2>&1 || exit $?
+  TT_EXPERIMENT_LIB=1 TT_T1_DEBUG=$d timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 100 --warmup 20 > $O/bench_$d.log 2>&1 || exit $?
   python - $O/bench_$d.log $d <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -7,7 +7,7 @@ O=gpurun_out/strips
 mkdir -p $O
 for i in 1 2; do
   for d in 0 128 256 384 896; do
-    TT_EXPERIMENT_LIB=1 TT_T1_DEBUG=$d timeout -k 10 200 python bench.py --no-cpu-baseline --steps 100 --warmup 20 > $O/b_${d}_$i.log 2>&1 || exit $?
+    TT_EXPERIMENT_LIB=1 TT_T1_DEBUG=$d timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 100 --warmup 20 > $O/b_${d}_$i.log 2>&1 || exit $?
     python - $O/b_${d}_$i.log $d <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

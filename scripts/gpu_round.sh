@@ -9,6 +9,7 @@ if [ $rc -ne 0 ]; then exit $rc; fi  # a failing test may be a GPU fault: run no
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1; rc=$?
 echo "smoke exit=$rc" >> gpurun_out/smoke.log; tail -2 gpurun_out/smoke.log
 if [ $rc -ne 0 ]; then exit $rc; fi
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the bench line with its roofline report and CPU leg, as before --full existed
 timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1; rc=$?
 echo "bench exit=$rc" >> gpurun_out/bench.log; tail -3 gpurun_out/bench.log
 if [ $rc -ne 0 ]; then exit $rc; fi

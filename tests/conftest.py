@@ -16,8 +16,11 @@ def pytest_configure(config):
 
 
 def load_golden(name: str) -> dict:
-    with np.load(GOLDEN / name, allow_pickle=False) as z:
-        d = {k: z[k] for k in z.files}
+    # a fixture too large for one committed file continues in <stem>.part1.npz, ... (make_golden.py)
+    d = {}
+    for part in [GOLDEN / name, *sorted(GOLDEN.glob(f"{Path(name).stem}.part*.npz"))]:
+        with np.load(part, allow_pickle=False) as z:
+            d.update({k: z[k] for k in z.files})
     # sparse_final fixtures (make_golden.py): dense final tables = initial tables with the changed
     # rows replaced; Adagrad states are zero outside them
     for k in [k for k in d if k.startswith("final_rows_")]:

@@ -79,6 +79,11 @@ def main():
     device = torch.device("cuda:0")  # every rank on the box's one GPU (the rehearsal)
     torch.cuda.set_device(device)
     dist.init_process_group("gloo")
+    from child_util import seed_all
+
+    # the model's init (table uniform_, nn.Linear) from a fixed seed, as the other DMP children: the
+    # logits' relative-error statistic depends on the weights drawn, so a failure must be repeatable
+    seed_all(0)
     import two_tower_recommender_model_amd as tt
 
     tt.install_torchrec_alias()

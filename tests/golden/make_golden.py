@@ -50,6 +50,28 @@ def load_reference_fragments(cat_cols):
     return ns
 
 
+PART_BYTES = 900_000  # a committed fixture file stays under 1 MiB
+
+
+def save_parts(path: Path, rec: dict) -> None:
+    """``rec`` as ``path`` (.npz, compressed); where that would pass PART_BYTES the arrays are dealt,
+    in order, into ``path`` and ``<stem>.part1.npz``, ``<stem>.part2.npz``, ... of at most PART_BYTES
+    of array data each (random fp32 barely compresses). tests/conftest.py:load_golden reads the
+    parts back into one dict."""
+    parts, size = [{}], 0
+    for k, v in rec.items():
+        n = np.asarray(v).nbytes
+        if parts[-1] and size + n > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = v
+        size += n
+    for old in path.parent.glob(path.stem + ".part*.npz"):
+        old.unlink()
+    for i, d in enumerate(parts):
+        np.savez_compressed(path if i == 0 else path.with_name(f"{path.stem}.part{i}.npz"), **d)
+
+
 def kjt_cases():
     """a1 golden vectors: the reference transform on int32/int64 columns with zeros, ids >= N,
     negative ids, and an all-zero batch."""
@@ -175,7 +197,7 @@ def train_case(name, num_users, num_items, D, B, layers, steps, seed, zipf=False
     for n, p in task.named_parameters():
         if "embedding_bags" not in n:
             rec["final_" + n] = p.detach().numpy()
-    np.savez_compressed(OUT / f"train_{name}.npz", **rec)
+    save_parts(OUT / f"train_{name}.npz", rec)
     print("train case:", name, "final loss", float(rec[f"s{steps-1}_loss"]))
 
 
