@@ -40,6 +40,7 @@ import torch
 from torch import nn
 
 from . import _lib, ops
+from .graph_pool import capture_graph
 
 
 def _named(obj, cls_name: str) -> bool:
@@ -298,15 +299,7 @@ class FusedDropin:
         self.graphs = []
         torch.cuda.synchronize(dev)
         for k in range(D):
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s):
-                    self._ring_step(k, k % 2, self.slot_cols[(k + 1) % D])
-            torch.cuda.current_stream(dev).wait_stream(s)
-            _lib.graph_upload(g, dev)
-            self.graphs.append(g)
+            self.graphs.append(capture_graph(dev, lambda: self._ring_step(k, k % 2, self.slot_cols[(k + 1) % D])))
         torch.cuda.synchronize(dev)
 
     # ---- staging -----------------------------------------------------------------------------
@@ -785,18 +778,11 @@ class FusedShardedDropin:
         self.graphs = []
         torch.cuda.synchronize(dev)
         for k in range(Dp):
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(device=dev)
-            s.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                    if self.mode == "kjt":
-                        self._kjt_step(k)
-                    else:
-                        self._pipelined(k, k % 2, self.slot_cols[(k + 2) % Dp])
-            torch.cuda.current_stream(dev).wait_stream(s)
-            _lib.graph_upload(g, dev)
-            self.graphs.append(g)
+            if self.mode == "kjt":
+                body = lambda: self._kjt_step(k)  # noqa: E731
+            else:
+                body = lambda: self._pipelined(k, k % 2, self.slot_cols[(k + 2) % Dp])  # noqa: E731
+            self.graphs.append(capture_graph(dev, body, thread_local=True))
         torch.cuda.synchronize(dev)
 
     # ---- staging -----------------------------------------------------------------------------

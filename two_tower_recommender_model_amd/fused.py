@@ -26,6 +26,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import FeatureMeta, check, id_dtype_code, ptr, ptr_array, stream_handle
+from .graph_pool import GraphPool, capture_graph, prefault_if_due, walk
 
 
 class FusedTwoTowerStep:
@@ -203,6 +204,13 @@ class FusedTwoTowerStep:
                            and self.qf == [0] and self.cf == [1] and self.layer_sizes == [128, 64]
                            and self.dims[0] == self.dims[1] and self.dims[0] in (64, 128))
         self.graph: Optional[torch.cuda.CUDAGraph] = None
+        # the graphs of the single-hot ring (capture_ring) and of the pool (capture_pool_kjt /
+        # capture_pool), empty until captured; each keeps its own cursor (ring_cursor, pool_cursor)
+        self._ring_pool = GraphPool(0, 1, None)
+        self._graph_pool = GraphPool(0, 1, None)
+        self.steps_per_graph = 1
+        self._pool_inputs: list = []  # resident inputs, alive as long as any graph may read them
+        self._prefault_due = False  # armed by a capture, consumed by the next replay
         # warm every scratch workspace so graph capture allocates nothing new (the all-zero batch
         # drops every id, so the tables are untouched; the towers' parameters are restored)
         p0 = self.params.clone()
@@ -261,24 +269,15 @@ class FusedTwoTowerStep:
         if k > 1 and (not ahead or n % k or k % 2):
             raise _lib.TTError("capture_pool_kjt: steps_per_graph > 1 needs ahead=True, an even k dividing the pool")
         self._prefault_due = True  # the next replay walks the tables' pages first (TableSet.prefault)
-        self._pool_inputs = getattr(self, "_pool_inputs", []) + [staged]
-        keep = self.values, self.offsets, self.labels
-        self.pool_graphs = []
-        self.pool_graphs_k = []
-        self.pool_mid = {}
-        self.pool_offset = 0
+        self._pool_inputs = self._pool_inputs + [staged]
+        self._graph_pool.clear()
         self.pool_ahead = bool(ahead)
         self._kjt_pool = staged
-        self._kjt_keep_graph = keep_graph
         if ahead:
             self.kjt_ring_prime(staged[0][0], staged[0][1], 0)
         self.steps_per_graph = k
-        try:
-            for i in range(n):
-                self.pool_graphs.append(self._capture_kjt_steps([self._kjt_item(i)], keep_graph))
-        finally:
-            self.values, self.offsets, self.labels = keep
-        self._kjt_groups(0)
+        # sync_weights only for the single-step graphs, the pool's first captures (not for regroups mid-run)
+        self._graph_pool = GraphPool(n, k, lambda idx: self._capture_kjt_steps(idx, keep_graph, sync=len(idx) == 1))
         self.graph = self.pool_graphs[-1]
         self.pool_cursor = 0
 
@@ -289,56 +288,30 @@ class FusedTwoTowerStep:
         nxt = (staged[(i + 1) % n][0], staged[(i + 1) % n][1]) if self.pool_ahead else None
         return v, o, lab, nxt, i % 2
 
-    def _kjt_groups(self, offset: int) -> None:
-        """The multi-step pool graphs grouped from pool position ``offset``: k-step graphs and (k a
-        power of two) k/2, ..., 2-step ones at the same alignment, so a run replays few graph
-        launches (a graph ends by joining its last step's side branches and the next one launches:
-        the stream idles ~20-40 us between two graphs, which single-step graphs pay every step)."""
-        n, k = len(self._kjt_pool), self.steps_per_graph
-        self.pool_offset = offset % n
-        self.pool_graphs_k, self.pool_mid = [], {}
-        if k < 2:
-            return
-        keep = self.values, self.offsets, self.labels
-        span = lambda j, sz: [self._kjt_item((offset + j + t) % n) for t in range(sz)]  # noqa: E731
-        try:
-            kg = self._kjt_keep_graph
-            self.pool_graphs_k = [self._capture_kjt_steps(span(j, k), kg, sync=False) for j in range(0, n, k)]
-            sz = k // 2 if k & (k - 1) == 0 else 0
-            while sz >= 2:
-                self.pool_mid[sz] = [self._capture_kjt_steps(span(j, sz), kg, sync=False) for j in range(0, n, sz)]
-                sz //= 2
-        finally:
-            self.values, self.offsets, self.labels = keep
-
     def align_pool(self, n_next: int = 0, after: int = 0) -> None:
         """Regroup the multi-step pool graphs for a run of ``n_next`` steps that starts ``after``
         steps from the cursor (the training state is untouched: only how the steps are grouped into
-        graph launches changes): the run replays its n_next % k remainder first, in aligned smaller
-        graphs, then n_next // k full graphs. Call it before the warm-up that precedes the run."""
-        k, n = self.steps_per_graph, len(self.pool_graphs)
-        off = (self.pool_cursor + after + (n_next % k)) % n
-        if k > 1 and off != self.pool_offset:
-            self._kjt_groups(off)
+        graph launches changes; GraphPool.align). Call it before the warm-up that precedes the run."""
+        self._graph_pool.align(self.pool_cursor, n_next, after)
 
-    def _capture_kjt_steps(self, items, keep_graph: bool, sync: bool = True):
-        """One HIP graph of consecutive multi-hot steps; items: (values, offsets, labels, next_kjt,
-        parity) per step. sync: refresh the bf16 weight copies first (not when regrouping mid-run)."""
+    def _capture_kjt_steps(self, idx, keep_graph: bool, sync: bool):
+        """One HIP graph of the multi-hot steps of pool positions ``idx`` (in order).
+        sync: refresh the bf16 weight copies first (not when regrouping mid-run)."""
         if sync:
             self.sync_weights()
         torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph(keep_graph=keep_graph)
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                for v, o, lab, nxt, par in items:
-                    self.values, self.offsets, self.labels = v, o, lab
-                    self.step(next_kjt=nxt, parity=par)
-                self.kjt_join()  # every forked stream rejoins inside the graph
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        if not keep_graph:
-            _lib.graph_upload(g, self.device)
+        keep = self.values, self.offsets, self.labels
+
+        def body():
+            for i in idx:
+                self.values, self.offsets, self.labels, nxt, par = self._kjt_item(i)
+                self.step(next_kjt=nxt, parity=par)
+            self.kjt_join()  # every forked stream rejoins inside the graph
+
+        try:
+            g = capture_graph(self.device, body, keep_graph=keep_graph)
+        finally:
+            self.values, self.offsets, self.labels = keep
         torch.cuda.synchronize(self.device)
         return g
 
@@ -346,7 +319,7 @@ class FusedTwoTowerStep:
         """Make the current stream wait for the next batch's grouping a pipelined multi-hot step left
         running on the side stream (the following step joins it before its update; a captured graph
         and any other use join it here)."""
-        ev = getattr(self, "_prep_event", None)
+        ev = self._prep_event
         if ev is not None:
             torch.cuda.current_stream(self.device).wait_event(ev)
             self._prep_event = None
@@ -362,38 +335,19 @@ class FusedTwoTowerStep:
     def replay_pool(self, n: int) -> None:
         """Replay n pool graphs in pool order, continuing at the cursor (the pipelined pool needs
         the order: graph i expects batch i's grouping from graph i-1)."""
-        if getattr(self, "_prefault_due", False):  # first replay after a capture: the tables' pages
-            self._prefault_due = False  # walked right before it (TableSet.prefault; r06pf_* profiles)
-            self.tables.prefault()
-        i, nb = self.pool_cursor, len(self.pool_graphs)
-        k = getattr(self, "steps_per_graph", 1)
-        mid = getattr(self, "pool_mid", {})
-        off = getattr(self, "pool_offset", 0)
-        while n > 0:
-            r = (i - off) % nb  # position relative to the multi-step graphs' grouping
-            if k > 1 and self.pool_graphs_k and r % k == 0 and n >= k:
-                self.pool_graphs_k[r // k].replay()
-                sz = k
-            else:
-                sz = next((m for m in sorted(mid, reverse=True) if r % m == 0 and n >= m), 1)
-                (mid[sz][r // sz] if sz > 1 else self.pool_graphs[i]).replay()
-            i, n = (i + sz) % nb, n - sz
-        self.pool_cursor = i
+        prefault_if_due(self)
+        self.pool_cursor = self._graph_pool.walk(self.pool_cursor, n)
 
     def pool_step_eager(self) -> None:
         """One step of the captured multi-hot pool at the cursor without graphs (timing / tests)."""
-        staged, i = self._kjt_pool, self.pool_cursor
-        n = len(staged)
+        i = self.pool_cursor
         keep = self.values, self.offsets, self.labels
-        self.values, self.offsets, self.labels = staged[i]
+        self.values, self.offsets, self.labels, nxt, par = self._kjt_item(i)
         try:
-            if self.pool_ahead:
-                self.step(next_kjt=(staged[(i + 1) % n][0], staged[(i + 1) % n][1]), parity=i % 2)
-            else:
-                self.step()
+            self.step(next_kjt=nxt, parity=par)
         finally:
             self.values, self.offsets, self.labels = keep
-        self.pool_cursor = (i + 1) % n
+        self.pool_cursor = (i + 1) % len(self._kjt_pool)
 
     def _towers_fwd(self):
         L = len(self.layer_sizes)
@@ -749,92 +703,75 @@ class FusedTwoTowerStep:
         n = len(batches)
         if k < 1 or n % k or n % 2:
             raise _lib.TTError("capture_ring: the batch count must be even and a multiple of steps_per_graph")
-        staged = []
-        for cols, labels in batches:
-            for c in cols:
-                if c.dtype != self.id_dtype or not c.is_contiguous() or c.numel() != self.B:
-                    raise _lib.TTError("capture_ring: batch columns must match the step's id dtype and batch")
-            staged.append((list(cols), labels.to(torch.int32).contiguous()))
-        self._ring_inputs = staged
+        self._ring_inputs = staged = self._staged_cols(batches, "capture_ring")
         self._prefault_due = True  # the next replay walks the tables' pages first (TableSet.prefault)
         self.ring_reset()
         self.sync_weights()
         self.ring_prime(staged[0][0], 0)
         torch.cuda.synchronize(self.device)
         self.ring_cursor = 0
-        self.ring_k = k
-        self._ring_keep = keep_graph
-        self.ring_small = [self._ring_graph([i]) for i in range(n)]
-        self._ring_groups(0)
 
-    def _ring_graph(self, idx) -> torch.cuda.CUDAGraph:
-        """One HIP graph of the production steps of pool batches ``idx`` (in order)."""
-        staged, n = self._ring_inputs, len(self._ring_inputs)
-        g = torch.cuda.CUDAGraph(keep_graph=self._ring_keep)
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
+        def cap(idx):
+            def body():
                 for i in idx:
                     self.ring_step(staged[i][0], staged[i][1], i % 2, staged[(i + 1) % n][0])
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        if not self._ring_keep:  # keep_graph: instantiated later, by its user
-            _lib.graph_upload(g, self.device)
-        return g
 
-    def _ring_groups(self, offset: int) -> None:
-        """The multi-step graphs, grouped from pool position ``offset``: k-step graphs, and (k a
-        power of two) k/2, k/4, ..., 2-step ones at the same alignment, so a run replays few graph
-        launches (one costs the host ~35-55 us, about one step of GPU time: single-step graphs leave
-        the GPU idle between them)."""
-        n, k = len(self._ring_inputs), self.ring_k
-        span = lambda j, sz: [(offset + j + t) % n for t in range(sz)]  # noqa: E731
-        self.ring_offset = offset % n
-        self.ring_graphs = [self._ring_graph(span(j, k)) for j in range(0, n, k)] if k > 1 else list(self.ring_small)
-        self.ring_mid = {}
-        self._prefault_due = True  # the next replay walks the tables' pages first (TableSet.prefault)
-        sz = k // 2 if k & (k - 1) == 0 else 0
-        while sz >= 2:
-            self.ring_mid[sz] = [self._ring_graph(span(j, sz)) for j in range(0, n, sz)]
-            sz //= 2
+            return capture_graph(self.device, body, keep_graph=keep_graph)
+
+        self._ring_pool = GraphPool(n, k, cap)
         torch.cuda.synchronize(self.device)
+
+    def _staged_cols(self, batches: Sequence, who: str) -> list:
+        """The resident single-hot batches as [(cols, int32 labels)], checked against the step."""
+        staged = []
+        for cols, labels in batches:
+            for c in cols:
+                if c.dtype != self.id_dtype or not c.is_contiguous() or c.numel() != self.B:
+                    raise _lib.TTError(f"{who}: batch columns must match the step's id dtype and batch")
+            staged.append((list(cols), labels.to(torch.int32).contiguous()))
+        return staged
 
     def align_ring(self, n_next: int = 0, after: int = 0) -> None:
         """Regroup the multi-step graphs for a run of ``n_next`` steps that starts ``after`` steps
         from the cursor (the training state is untouched: only how the steps are grouped into graph
-        launches changes): that run replays its n_next % k remainder first, in aligned smaller
-        graphs (the first launch is the cheapest: the GPU starts sooner), then n_next // k full
-        graphs — no single-step graphs when the remainder is a sum of the captured sizes."""
-        off = (self.ring_cursor + after + (n_next % self.ring_k)) % len(self.ring_small)
-        if self.ring_k > 1 and off != self.ring_offset:
-            self._ring_groups(off)
+        launches changes; GraphPool.align)."""
+        if self._ring_pool.align(self.ring_cursor, n_next, after):
+            self._prefault_due = True  # the next replay walks the tables' pages first (TableSet.prefault)
+            torch.cuda.synchronize(self.device)
 
     def run(self, n: int) -> None:
-        """Replay n production steps from the ring, continuing at the cursor."""
-        if getattr(self, "_prefault_due", False):  # first replay after a capture: the tables' pages
-            self._prefault_due = False  # walked right before it (TableSet.prefault; r06pf_* profiles)
-            self.tables.prefault()
-        i, nb, k = self.ring_cursor, len(self.ring_small), self.ring_k
-        mid = self.ring_mid
-        while n > 0:
-            r = (i - self.ring_offset) % nb  # position relative to the graphs' grouping
-            if r % k == 0 and n >= k:
-                self.ring_graphs[r // k].replay()
-                sz = k
-            else:
-                sz = next((m for m in sorted(mid, reverse=True) if r % m == 0 and n >= m), 1)
-                (mid[sz][r // sz] if sz > 1 else self.ring_small[i]).replay()
-            i, n = (i + sz) % nb, n - sz
-        self.ring_cursor = i
+        """Replay n production steps from the ring, continuing at the cursor (needs only the
+        ``ring_*`` lists; the prefault flag may be absent)."""
+        if getattr(self, "_prefault_due", False):
+            prefault_if_due(self)
+        self.ring_cursor = walk(self.ring_cursor, n, self.ring_k, self.ring_offset, self.ring_small, self.ring_graphs,
+                                self.ring_mid)
+
+    # views of the two pools (ring_graphs is ring_small when k == 1; pool_graphs: the single-step
+    # graphs after capture_pool_kjt, the k-step graphs after capture_pool)
+    ring_small = property(lambda self: self._ring_pool.small)
+    ring_graphs = property(lambda self: self._ring_pool.big)
+    ring_mid = property(lambda self: self._ring_pool.mid)
+    ring_offset = property(lambda self: self._ring_pool.offset)
+    ring_k = property(lambda self: self._ring_pool.k)
+    pool_graphs = property(lambda self: self._graph_pool.small)
+    pool_graphs_k = property(lambda self: self._graph_pool.big if self._graph_pool.k > 1 else [])
+    pool_mid = property(lambda self: self._graph_pool.mid)
+    pool_offset = property(lambda self: self._graph_pool.offset)
 
     def timed_ring(self, n: int) -> dict:
         """n eager production steps (from the cursor) with a HIP event pair around every launch;
         mean device time (ms) per launch name."""
+        return self._timed(n, lambda i: self.run_eager(1))
+
+    def _timed(self, n: int, one_step) -> dict:
+        """``one_step(i)`` for i < n with per-launch timing on (``_mark``); the mean device time
+        (ms) per launch name."""
         self._timing = []
         try:
-            for _ in range(n):
+            for i in range(n):
                 self._timing.append({})
-                self.run_eager(1)
+                one_step(i)
             torch.cuda.synchronize(self.device)
             acc = {}
             for m in self._timing:
@@ -860,30 +797,24 @@ class FusedTwoTowerStep:
         resident (cols, labels) device batches) the graph holds one full step per batch, in order."""
         self.sync_weights()
         torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph(keep_graph=keep_graph)
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
         keep_cols, keep_labels = self.cols, self.labels
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                if batches is None:
-                    self.step(next_kjt=next_kjt, parity=parity)
-                else:
-                    for cols, labels in batches:
-                        self.cols, self.labels = list(cols), labels
-                        self.step()
+
+        def body():
+            if batches is None:
+                self.step(next_kjt=next_kjt, parity=parity)
+            else:
+                for cols, labels in batches:
+                    self.cols, self.labels = list(cols), labels
+                    self.step()
+
+        g = capture_graph(self.device, body, keep_graph=keep_graph)
         self.cols, self.labels = keep_cols, keep_labels
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        if not keep_graph:
-            _lib.graph_upload(g, self.device)
         torch.cuda.synchronize(self.device)
         self.graph = g
 
     def replay(self, i: Optional[int] = None) -> None:
         """Replay the single-step graph, or pool graph ``i`` (which runs ``steps_per_graph`` steps)."""
-        if getattr(self, "_prefault_due", False):  # first replay after a capture: the tables' pages
-            self._prefault_due = False  # walked right before it (TableSet.prefault; r06pf_* profiles)
-            self.tables.prefault()
+        prefault_if_due(self)
         if i is None:
             self.graph.replay()
         else:
@@ -893,22 +824,16 @@ class FusedTwoTowerStep:
         """Run n eager steps over the resident batches with a HIP event pair around every launch on
         its stream; returns the mean device time (ms) per launch name."""
         keep = self.cols, self.labels
-        self._timing = []
+
+        def one_step(i):
+            cols, labels = batches[i % len(batches)]
+            self.cols, self.labels = list(cols), labels.to(torch.int32)
+            self.step()
+
         try:
-            for i in range(n):
-                cols, labels = batches[i % len(batches)]
-                self.cols, self.labels = list(cols), labels.to(torch.int32)
-                self._timing.append({})
-                self.step()
-            torch.cuda.synchronize(self.device)
-            acc = {}
-            for m in self._timing:
-                for name, (a, b) in m.items():
-                    acc.setdefault(name, []).append(a.elapsed_time(b))
+            return self._timed(n, one_step)
         finally:
-            self._timing = None
             self.cols, self.labels = keep
-        return {k: sum(v) / len(v) for k, v in acc.items()}
 
     def capture_pool(self, batches: Sequence, steps_per_graph: int = 1, keep_graph: bool = False) -> None:
         """Graphs over resident input batches ((cols, labels) device tensors), read in place so a
@@ -918,16 +843,14 @@ class FusedTwoTowerStep:
         k = int(steps_per_graph)
         if k < 1 or len(batches) % k:
             raise _lib.TTError("capture_pool: the batch count must be a multiple of steps_per_graph")
-        staged = []
-        for cols, labels in batches:
-            for c in cols:
-                if c.dtype != self.id_dtype or not c.is_contiguous() or c.numel() != self.B:
-                    raise _lib.TTError("capture_pool: batch columns must match the step's id dtype and batch")
-            staged.append((list(cols), labels.to(torch.int32).contiguous()))
-        self._pool_inputs = getattr(self, "_pool_inputs", []) + [staged]  # alive as long as any graph
+        staged = self._staged_cols(batches, "capture_pool")
+        self._pool_inputs = self._pool_inputs + [staged]  # alive as long as any graph
         self._prefault_due = True  # the next replay walks the tables' pages first (TableSet.prefault)
-        self.pool_graphs = []
-        for j in range(0, len(staged), k):
-            self.capture(staged[j:j + k], keep_graph=keep_graph)
-            self.pool_graphs.append(self.graph)
+        self._graph_pool.clear()
+
+        def cap(idx):  # pool position j: the k batches of graph j, as one unit (replayed by index)
+            self.capture(staged[idx[0] * k:idx[0] * k + k], keep_graph=keep_graph)
+            return self.graph
+
+        self._graph_pool = GraphPool(len(staged) // k, 1, cap)
         self.steps_per_graph = k

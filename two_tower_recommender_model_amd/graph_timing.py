@@ -1,7 +1,7 @@
 """Per-launch device time INSIDE a replayed HIP graph, with HIP events (bench instrumentation).
 
 torch refuses external (graph-node) events on ROCm, so this edits the captured graph directly:
-capture with ``torch.cuda.CUDAGraph(keep_graph=True)``, then for each kernel node of the linear
+capture with ``keep_graph=True`` (graph_pool.capture_graph), then for each kernel node of the linear
 launch chain insert an event-record node before and after it (hipGraphAddEventRecordNode + edge
 rewiring), instantiate, replay, and read hipEventElapsedTime per pair. The events are recorded on
 the stream the graph (and so each kernel) runs on.

@@ -44,6 +44,7 @@ import torch.distributed as dist
 
 from . import _lib, ops
 from ._lib import FeatureMeta, ShardSeg, check, id_dtype_code, ptr, ptr_array, stream_handle
+from .graph_pool import GraphPool, capture_graph, prefault_if_due
 
 
 # ---- collectives --------------------------------------------------------------------------------
@@ -884,8 +885,9 @@ class FusedShardedTwoTowerStep:
             self._wB = comm.wait_desc(self.rows_in)
         self.overlap = bool(overlap)
         self.side = torch.cuda.Stream(device=dev) if self.overlap else None
-        self.pool_graphs: list = []
-        self.small_graphs: list = []
+        self._pool = GraphPool(0, 1, None)  # the pipelined pool's graphs (capture_pool), empty until captured
+        self._pool_inputs: list = []
+        self._prefault_due = False  # armed by a capture, consumed by the next run
         self.cursor = None  # pipelined pool: index of the batch whose rows are staged in rows_in
         torch.cuda.synchronize(dev)
 
@@ -1248,8 +1250,7 @@ class FusedShardedTwoTowerStep:
         """Drop the captured graphs (before tearing down the process group: a live graph holds
         references to the RCCL communicator's work)."""
         torch.cuda.synchronize(self.device)
-        self.pool_graphs = []
-        self.small_graphs = []
+        self._pool.clear()
         self._pool_inputs = []
         import gc
 
@@ -1286,7 +1287,6 @@ class FusedShardedTwoTowerStep:
             raise _lib.TTError("capture_pool: the batch count must be even and a multiple of steps_per_graph")
         staged = self._staged(batches)
         self._pool_inputs = [staged]
-        self.pool_k = k
         self._prefault_due = True  # the next replay walks the tables' pages first (TableSet.prefault)
         # stage batch 0 (and place batch 1's keys) eagerly, then retire every eager collective
         self.prime(staged[0][0], 0, staged[1][0])
@@ -1294,44 +1294,33 @@ class FusedShardedTwoTowerStep:
         self.comm.retire()
 
         def cap(idx):
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(device=self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                    for i in idx:
-                        self.step_pipelined(staged[i][1], i % 2, staged[(i + 2) % n][0])
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            _lib.graph_upload(g, self.device)  # no upload inside the first (timed) launch
-            return g
+            def body():
+                for i in idx:
+                    self.step_pipelined(staged[i][1], i % 2, staged[(i + 2) % n][0])
+
+            # thread_local: the RCCL watchdog's pending works are retired above
+            return capture_graph(self.device, body, thread_local=True)
 
         torch.cuda.synchronize(self.device)
-        self.pool_graphs = [cap(range(j, j + k)) for j in range(0, n, k)]
-        self.small_graphs = [cap([i]) for i in range(n)] if k > 1 else list(self.pool_graphs)
+        self._pool = GraphPool(n, k, cap, halves=False)
         torch.cuda.synchronize(self.device)
+
+    # pool_graphs[j]: the k steps from batch j*k; small_graphs[i]: batch i alone (the same graphs when k == 1)
+    pool_graphs = property(lambda self: self._pool.big)
+    small_graphs = property(lambda self: self._pool.small)
+    pool_k = property(lambda self: self._pool.k)
 
     def run(self, n: int) -> None:
         """Replay n pipelined steps from the pool, continuing at the cursor (re-primed at the pool's
         first batch after ``reset_pipeline`` / ``load_state_dict``)."""
-        if getattr(self, "_prefault_due", False):  # first replay after a capture: the tables' pages
-            self._prefault_due = False  # walked right before it (TableSet.prefault; r06pf_* profiles)
-            self.tables.prefault()
+        prefault_if_due(self)
         if not self.small_graphs:
             raise _lib.TTError("run: no captured pool (capture_pool first)")
         if self.cursor is None:
             staged = self._pool_inputs[0]
             self.prime(staged[0][0], 0, staged[1][0])
             self.cursor = 0
-        i, nb, k = self.cursor, len(self.small_graphs), self.pool_k
-        while n > 0:
-            if i % k == 0 and n >= k:
-                self.pool_graphs[i // k].replay()
-                i, n = i + k, n - k
-            else:
-                self.small_graphs[i].replay()
-                i, n = i + 1, n - 1
-            i %= nb
-        self.cursor = i
+        self.cursor = self._pool.walk(self.cursor, n)
 
     def run_eager(self, batches: Sequence, n: int) -> None:
         """n pipelined steps over a cyclic pool without graphs (continuing at the cursor)."""

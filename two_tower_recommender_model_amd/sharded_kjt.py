@@ -47,6 +47,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check, id_dtype_code, ptr, stream_handle
+from .graph_pool import GraphPool, capture_graph, prefault_if_due
 
 
 def route_counts(values: torch.Tensor, offsets: torch.Tensor, B: int, num_embeddings: Sequence[int],
@@ -210,8 +211,9 @@ class FusedShardedKJTStep:
         self.gpooled = torch.zeros(B, F * D, dtype=torch.float32, device=dev)
         self.logits = torch.empty(B, dtype=torch.float32, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
-        self.graphs: list = []
+        self._pool = GraphPool(0, 1, None)  # one graph per resident batch (capture_pool), empty until captured
         self._pool_inputs: list = []
+        self._prefault_due = False  # armed by a capture, consumed by the next run
         torch.cuda.synchronize(dev)
 
     def layer_views(self):
@@ -310,21 +312,16 @@ class FusedShardedKJTStep:
         self._prefault_due = True  # the next replay walks the tables' pages first (TableSet.prefault)
         self.warmup()
         self.comm.retire()
-        self.graphs = []
-        for v, o, l in staged:
-            g = torch.cuda.CUDAGraph()
-            s = torch.cuda.Stream(device=self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                # thread_local: only this thread's calls are checked against the capture (the RCCL
-                # watchdog's pending works are retired above, TorchComm.retire)
-                with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
-                    self.step(v, o, l)
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            _lib.graph_upload(g, self.device)
-            self.graphs.append(g)
+        self._pool.clear()
+
+        def cap(idx):  # thread_local: the RCCL watchdog's pending works are retired above (TorchComm.retire)
+            return capture_graph(self.device, lambda: self.step(*staged[idx[0]]), thread_local=True)
+
+        self._pool = GraphPool(len(staged), 1, cap)
         torch.cuda.synchronize(self.device)
         self.cursor = 0
+
+    graphs = property(lambda self: self._pool.small)
 
     def warmup(self) -> None:
         """One eager step on a batch of empty bags (communicators, workspaces, kernels) that leaves the
@@ -341,12 +338,8 @@ class FusedShardedKJTStep:
         torch.cuda.synchronize(self.device)
 
     def run(self, n: int) -> None:
-        if getattr(self, "_prefault_due", False):  # first replay after a capture: the tables' pages
-            self._prefault_due = False  # walked right before it (TableSet.prefault; r06pf_* profiles)
-            self.tables.prefault()
-        for _ in range(n):
-            self.graphs[self.cursor].replay()
-            self.cursor = (self.cursor + 1) % len(self.graphs)
+        prefault_if_due(self)
+        self.cursor = self._pool.walk(self.cursor, n)
 
     def run_eager(self, batches: Sequence, n: int, start: int = 0) -> None:
         for i in range(n):
@@ -373,7 +366,7 @@ class FusedShardedKJTStep:
 
     def release_graphs(self) -> None:
         torch.cuda.synchronize(self.device)
-        self.graphs = []
+        self._pool.clear()
         self._pool_inputs = []
         import gc
 
