@@ -84,6 +84,73 @@ def block_bucketize(lengths: np.ndarray, values: np.ndarray, F_: int, B: int,
     return new_len.reshape(-1), np.asarray(new_vals, dtype=values.dtype)
 
 
+def block_bucketize_fast(lengths: np.ndarray, values: np.ndarray, F_: int, B: int,
+                         block_sizes: Sequence[int], W: int):
+    """block_bucketize vectorised: a stable sort of the ids by (bucket, bag) keeps the input order
+    inside one (bucket, bag), which is the loop's order."""
+    lengths = np.asarray(lengths)
+    values = np.asarray(values)
+    n = F_ * B
+    bag = np.repeat(np.arange(n, dtype=np.int64), lengths)
+    bs = np.asarray(block_sizes, np.int64)[bag // max(B, 1)] if values.size else np.zeros(0, np.int64)
+    v = values.astype(np.int64)
+    inside = v < bs * W
+    p = np.where(inside, v // np.maximum(bs, 1), v % W)
+    loc = np.where(inside, v % np.maximum(bs, 1), v // W)
+    key = p * n + bag
+    order = np.argsort(key, kind="stable")
+    new_len = np.bincount(key, minlength=W * n).astype(np.int32)
+    return new_len, loc[order].astype(values.dtype)
+
+
+def kjt_single_hot_cols(values: np.ndarray, offsets: np.ndarray, F_: int, B: int, num_embeddings: Sequence[int]):
+    """The glue between a single-hot KJT and the fused step's id columns (dropin.py; no TorchRec
+    counterpart): cols[f][b] = 0 for an empty bag, the bag's value v, or N_f for v == 0. A bag of more
+    than one id sets bit 0 of err, a value outside [0, N_f) bit 1; such bags get 0. Returns
+    (cols int64 [F, B], err)."""
+    offsets = np.asarray(offsets, np.int64)
+    cols = np.zeros((F_, B), np.int64)
+    err = 0
+    for f in range(F_):
+        n = int(num_embeddings[f])
+        for b in range(B):
+            s, e = offsets[f * B + b], offsets[f * B + b + 1]
+            if e - s == 1:
+                v = int(values[s])
+                if v < 0 or v >= n:
+                    err |= 2
+                else:
+                    cols[f, b] = n if v == 0 else v
+            elif e - s != 0:
+                err |= 1
+    return cols, err
+
+
+def kjt_admit(values: np.ndarray, offsets: np.ndarray, F_: int, B: int, num_embeddings: Sequence[int],
+              block_sizes: Sequence[int], owners: Sequence[int], W: int) -> np.ndarray:
+    """Admission counts of one KJT batch (dropin.FusedShardedDropin): out[0] = 1 if a bag holds more
+    than one id, out[1] = 2 if a value lies outside [0, N_f) (such a value is counted nowhere),
+    out[2 + d * F + f] = the ids of feature f owned by d (row-wise: id // block; table-wise:
+    owners[f]). int32 [2 + W * F]."""
+    offsets = np.asarray(offsets, np.int64)
+    out = np.zeros(2 + W * F_, np.int32)
+    if (np.diff(offsets[:F_ * B + 1]) > 1).any():
+        out[0] = 1
+    for f in range(F_):
+        v = np.asarray(values[offsets[f * B]:offsets[(f + 1) * B]]).astype(np.int64)
+        ok = (v >= 0) & (v < int(num_embeddings[f]))
+        if not ok.all():
+            out[1] = 2
+        v = v[ok]
+        if block_sizes[f] > 0:
+            d = v // int(block_sizes[f])
+        else:
+            d = np.full(v.size, int(owners[f]), np.int64)
+        d = d[(d >= 0) & (d < W)]
+        out[2 + np.arange(W) * F_ + f] += np.bincount(d, minlength=W).astype(np.int32)
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # a4: EBC sum pooling — torchrec EmbeddingBagCollection.forward (unsharded CPU): one
 # nn.EmbeddingBag(mode="sum", include_last_offset=True) per table (self.ebc(kjt), 03:417)
@@ -161,9 +228,12 @@ def dot_bce(q: torch.Tensor, c: torch.Tensor, labels: torch.Tensor):
 
 
 def adam(params: List[torch.Tensor], grads: List[torch.Tensor], exp_avg, exp_avg_sq, step: int,
-         lr: float, beta1=0.9, beta2=0.999, eps=1e-8) -> None:
-    """torch.optim.Adam (amsgrad=False, weight_decay=0), single-tensor formula, in place."""
+         lr: float, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0) -> None:
+    """torch.optim.Adam (amsgrad=False), single-tensor formula, in place; weight_decay is torch's
+    L2 form, g + wd * p before the moment updates."""
     for p, g, m, v in zip(params, grads, exp_avg, exp_avg_sq):
+        if weight_decay != 0.0:
+            g = g.add(p, alpha=weight_decay)
         m.lerp_(g, 1 - beta1)
         v.mul_(beta2).addcmul_(g, g, value=1 - beta2)
         bc1 = 1 - beta1 ** step
@@ -358,7 +428,7 @@ def rowwise_adagrad_from_lookups(table: torch.Tensor, state: torch.Tensor, rows:
     if rows.numel() == 0:
         return
     u, inv = torch.unique(rows, return_inverse=True)
-    g = torch.zeros(u.numel(), table.shape[1])
+    g = torch.zeros(u.numel(), table.shape[1], dtype=grad_rows.dtype)
     g.index_add_(0, inv, grad_rows)
     rowwise_adagrad_sparse(table, state, u, g, lr, eps)
 

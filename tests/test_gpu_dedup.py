@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from edge_cases import assert_clean as _assert_clean
 from oracle import ref
 
 pytestmark = pytest.mark.gpu
@@ -72,25 +73,6 @@ def test_dedup_cols_vs_oracle(ops, device, B, dims, zipf):
         np.testing.assert_allclose(got_s.numpy(), states[t].numpy(), rtol=1e-4, atol=1e-9)
         np.testing.assert_allclose(got_w.numpy(), tables[t].numpy(), rtol=1e-4, atol=1e-6)
     _assert_clean(ts)
-
-
-def _assert_clean(ts):
-    """After every update the workspace is clean: every slot free, hot-row counters zero, no
-    deferred insert pending (dedup.hip dedup_layout: slots, keys, hot list, counters, claims,
-    overflow entries)."""
-    L = ts._dd_cap
-    cap = 1024
-    while cap < 16 * L:
-        cap <<= 1
-    al = lambda x: (x + 255) // 256 * 256  # noqa: E731
-    sl = ts._dd_ws[:cap * 128].view(torch.int64).view(cap, 16).cpu()  # 128-B slots
-    assert bool((sl[:, 0] == -1).all())
-    o = cap * 128 + al(8 * L) + al(4 * (L // 31 + 1))
-    assert ts._dd_ws[o:o + 16].view(torch.int32).cpu().tolist() == [0, 0, 0, 0]
-    o_ovf = o + 256 + al(4 * L)
-    G = (L + 63) // 64
-    ovf = ts._dd_ws[o_ovf:o_ovf + 16 * 64 * G].view(torch.int64).view(G * 64, 2).cpu()
-    assert bool((ovf[:, 0] == -1).all())
 
 
 def test_dedup_cols_equals_kjt_path_when_not_hot(ops, device):

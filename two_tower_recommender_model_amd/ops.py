@@ -168,6 +168,28 @@ def block_bucketize(lengths: torch.Tensor, offsets: torch.Tensor, values: torch.
     return new_lengths, new_offsets, new_values
 
 
+def kjt_admit(values: torch.Tensor, offsets: torch.Tensor, F: int, B: int, num_embeddings: Sequence[int],
+              block_sizes: Sequence[int], owners: Sequence[int], W: int, out: Optional[torch.Tensor] = None):
+    """Admission counts of one key-major KJT batch (tt_kjt_admit): int32 [2 + W*F], zeroed by the call."""
+    _dev(offsets, out)
+    if offsets.dtype != torch.int32 or offsets.numel() != F * B + 1:
+        raise _lib.TTError("kjt_admit: offsets must be int32 [F*B + 1]")
+    nnz = values.numel()
+    if nnz:
+        _dev(values)
+    if out is None:
+        out = torch.empty(2 + W * F, dtype=torch.int32, device=offsets.device)
+    if out.dtype != torch.int32 or out.numel() < 2 + W * F or not out.is_contiguous():
+        raise _lib.TTError("kjt_admit: out must be contiguous int32 [2 + W*F]")
+    ne = (C.c_int64 * F)(*[int(n) for n in num_embeddings])
+    bs = (C.c_int64 * F)(*[int(b) for b in block_sizes])
+    ow = (C.c_int32 * F)(*[int(o) for o in owners])
+    check(_lib_().tt_kjt_admit(F, B, values.data_ptr() if nnz else None, id_dtype_code(values.dtype) if nnz else TT_I64,
+                               nnz, ptr(offsets), ne, bs, ow, W, ptr(out), stream_handle(offsets.device)),
+          "kjt_admit")
+    return out
+
+
 # ---- a4 / a8: embedding tables ----------------------------------------------------------------
 
 
@@ -502,11 +524,13 @@ class TableSet:
                                 dedup_max_lookups=self._dd_cap, multi_only=multi_only)
 
     def bwd_dense(self, grad_out: torch.Tensor, values: torch.Tensor, offsets: torch.Tensor, B: int,
-                  grad_weights: torch.Tensor, pooling: int = TT_POOL_SUM) -> None:
+                  grad_weights: torch.Tensor, pooling: int = TT_POOL_SUM, bounds_check: bool = False) -> None:
+        """bounds_check: ids outside [0, num_rows) add to row 0 (as pooled_fwd reads row 0 for them)."""
         _dev(grad_out, grad_weights)
         idt = id_dtype_code(values.dtype) if values.numel() else TT_I64
         check(_lib_().tt_pooled_bwd_dense(self._tm, self.T, self._fm, self.F, B, ptr(grad_out), grad_out.stride(0),
-                                          ptr(values), idt, ptr(offsets), pooling, ptr(grad_weights), 0,
+                                          ptr(values), idt, ptr(offsets), pooling, ptr(grad_weights),
+                                          1 if bounds_check else 0,
                                           stream_handle(self.device)), "pooled_bwd_dense")
 
 
