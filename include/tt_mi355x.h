@@ -40,6 +40,8 @@
  *                              <- both MLP towers (03:411-412, :420-436) + TwoTowerTrainTask
  *                                 (03:447-455) + loss.backward() through the towers + the dense
  *                                 Adam step (03:826-829), as three fused kernels
+ *   tt_topk_mips               <- the vector-index query loop of 04_evaluate_retrieval.py:131-153
+ *                                 (exact top-k by inner product over the exported item embeddings)
  *   tt_launch (a launch plan)  <- the same backward work with several roles in one launch: the
  *                                 weight gradients beside the embedding update / next-batch insert /
  *                                 shard route and gather ("launch plans" below)
@@ -589,6 +591,32 @@ int tt_kjt_admit(int F, int64_t B, const void* values, int id_dtype, int64_t nnz
  * written except, never in practice, one word of `sink` (device, 4 bytes). page_bytes: a multiple
  * of 4 (4096 = the GPU page). ABI 4. */
 int tt_table_prefault(const void* base, size_t bytes, size_t page_bytes, uint32_t* sink, void* stream);
+
+/* Exact top-k maximum-inner-product retrieval (ABI 4 addition). Replaces the query loop of
+ * 04_evaluate_retrieval.py:131-153 (every test user's embedding queried against the vector index of
+ * the item embeddings built at :125-129, k = 100): for each of M queries the k items of highest
+ * score s(m, n) = sum_e Q[m, e] * C[n, e] (+ bias[n] when bias is not NULL), selected exactly.
+ * Q [M, E] and C [N, E] are fp32 or bf16 (TT_F32 / TT_BF16) with row strides ldq / ldc in elements
+ * (the fp32 output of the embedding export is consumed in place); fp32 operands are rounded to bf16
+ * (round-to-nearest-even) on load, the products are summed on bf16 MFMA with fp32 accumulation in a
+ * fixed order over E, bias (fp32 [N]) is added last. A pair's score is therefore a function of the
+ * two rows' bf16 values and bias[n] only — not of M, N, a row's position or the split count.
+ * ids [M, k] (int64, row indices into C) and scores [M, k] (fp32) hold each query's list sorted by
+ * the total order "higher score first, equal scores by lower index", so the result is unique and
+ * bit-identical from run to run and across split counts; when N < k the tail is id -1, score -inf.
+ * bias[n] = -0.5 * |C[n]|^2 ranks by ascending L2 distance. Two kernels: the fused score + select
+ * over (query tiles x item splits), and the merge of the splits' partial lists; `splits` = 0 lets
+ * the library choose (so that a small M still fills the chip), 1..64 fixes it. The workspace
+ * (splits * M * k * 8 bytes; never a score matrix) need not be initialised.
+ * Limits (TT_EINVAL otherwise, before any launch): E a multiple of 32 in [32, 128]; 1 <= k <=
+ * TT_TOPK_MAX_K; M >= 1; 1 <= N < 2^31. Scores must be finite: NaN (and -inf) scores are not
+ * supported (a NaN score is never selected). tt_topk_mips_workspace_bytes returns 0 for arguments
+ * outside the limits. */
+#define TT_TOPK_MAX_K 256
+size_t tt_topk_mips_workspace_bytes(int64_t M, int64_t N, int k, int splits);
+int tt_topk_mips(const void* queries, int q_dtype, int64_t ldq, const void* items, int c_dtype, int64_t ldc,
+                 const float* bias, int64_t M, int64_t N, int E, int k, int splits, int64_t* ids, float* scores,
+                 void* workspace, size_t ws_bytes, void* stream);
 
 /* SETUP ONLY (allocating, synchronising): device memory for embedding tables on the current
  * device, physically contiguous when the driver can give it (hipDeviceMallocContiguous: the largest

@@ -1,0 +1,109 @@
+"""Exact top-k retrieval (ops.topk_mips: tt_topk_mips, the fused score + select kernel) against the
+torch composition on the same GPU: bf16 torch.matmul over item chunks, torch.topk of each score
+chunk and a running merge of the best k. Interleaved runs of the two arms after a warm-up, timed with
+HIP events; prints one JSON line (medians, the runs, the spread). Inputs are seeded, generated on the
+device; nothing is read from outside the tree.
+
+    python scripts/bench_retrieval.py                       # M 4096, N 4,194,304, E 64, k 100
+    python scripts/bench_retrieval.py --M 10000 --N 100000000 --items bf16 --no-baseline --runs 1
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from two_tower_recommender_model_amd import ops  # noqa: E402
+
+
+def torch_arm(q16, c16, k, chunk):
+    best_s = best_i = None
+    for lo in range(0, c16.shape[0], chunk):
+        s = q16 @ c16[lo:lo + chunk].T  # [M, chunk] bf16: the score chunk goes through HBM
+        v, i = torch.topk(s, min(k, s.shape[1]), dim=1)
+        i = i + lo
+        if best_s is None:
+            best_s, best_i = v, i
+        else:
+            v, j = torch.topk(torch.cat([best_s, v], 1), k, dim=1)
+            best_s, best_i = v, torch.cat([best_i, i], 1).gather(1, j)
+    return best_i, best_s
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--M", type=int, default=4096)
+    ap.add_argument("--N", type=int, default=4194304)
+    ap.add_argument("--E", type=int, default=64)
+    ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--items", choices=["f32", "bf16"], default="f32", help="item dtype of the fused arm")
+    ap.add_argument("--chunk", type=int, default=65536, help="items per matmul of the torch arm")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--splits", type=int, default=None)
+    ap.add_argument("--no-baseline", action="store_true")
+    a = ap.parse_args()
+
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    q = torch.randn(a.M, a.E, device=dev, generator=g) * 0.5
+    gen_dtype = torch.float32 if a.items == "f32" else torch.bfloat16
+    c = torch.empty(a.N, a.E, dtype=gen_dtype, device=dev)
+    for lo in range(0, a.N, 1 << 22):  # in pieces: the generator's fp32 temporary stays small
+        c[lo:lo + (1 << 22)] = torch.randn(min(1 << 22, a.N - lo), a.E, device=dev, generator=g) * 0.5
+    q16 = q.to(torch.bfloat16)
+    c16 = c if a.items == "bf16" or a.no_baseline else c.to(torch.bfloat16)  # the torch arm's operands (not timed)
+
+    def fused():
+        return ops.topk_mips(q, c, a.k, splits=a.splits)
+
+    def composed():
+        return torch_arm(q16, c16, a.k, a.chunk)
+
+    arms = {"fused": fused} if a.no_baseline else {"fused": fused, "torch": composed}
+    for _ in range(a.warmup):
+        for fn in arms.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {n: [] for n in arms}
+    outs = {}
+    for _ in range(a.runs):
+        for n, fn in arms.items():
+            t, outs[n] = timed(fn)
+            ms[n].append(round(t, 3))
+    res = {"bench": "retrieval", "M": a.M, "N": a.N, "E": a.E, "k": a.k, "items": a.items, "runs": a.runs,
+           "splits": a.splits, "device": torch.cuda.get_device_name(dev)}
+    flop = 2.0 * a.M * a.N * a.E
+    for n in arms:
+        med = statistics.median(ms[n])
+        res[n] = {"median_ms": med, "min_ms": min(ms[n]), "max_ms": max(ms[n]), "runs_ms": ms[n],
+                  "tflops": round(flop / med / 1e9, 1)}
+    res["item_bytes"] = c.numel() * c.element_size()
+    res["fused"]["item_stream_tb_s"] = round(res["item_bytes"] / res["fused"]["median_ms"] / 1e9, 3)
+    if not a.no_baseline:
+        res["speedup_median"] = round(res["torch"]["median_ms"] / res["fused"]["median_ms"], 2)
+        # slowest fused run against the fastest torch run: > 1 means faster by more than the spread
+        res["speedup_worst_case"] = round(res["torch"]["min_ms"] / res["fused"]["max_ms"], 2)
+        # agreement of the two arms' id sets (the torch arm ranks bf16-rounded scores: not exact)
+        fi, ti = outs["fused"][0], outs["torch"][0]
+        rows = slice(0, min(a.M, 256))
+        hit = (fi[rows].unsqueeze(2) == ti[rows].unsqueeze(1)).any(2).float().mean()
+        res["id_overlap_first_rows"] = round(float(hit), 4)
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -44,6 +44,7 @@ TT_POOL_SUM, TT_POOL_MEAN = 0, 1
 TT_TOWER_GENERAL_T1 = 1
 TT_MAX_FEATURES = 64
 TT_MAX_TABLES = 64
+TT_TOPK_MAX_K = 256
 
 
 class TableMeta(C.Structure):
@@ -325,6 +326,8 @@ SIGNATURES = {
     "tt_peer_exchange": (_int, [C.c_void_p, _vp, _vp, C.c_double, _vp]),
     "tt_kjt_admit": (_int, [_int, _i64, _vp, _int, _i64, _vp, _pi64, _pi64, _pi32, _int, _vp, _vp]),
     "tt_table_prefault": (_int, [_vp, _sz, _sz, _vp, _vp]),
+    "tt_topk_mips_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "tt_topk_mips": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "tt_table_alloc": (_int, [_sz, _pvp, C.POINTER(C.c_int)]),
     "tt_table_free": (_int, [_vp]),
 }
@@ -383,6 +386,7 @@ COMPUTE_ENTRY_POINTS = [
     "tt_peer_exchange",
     "tt_kjt_admit",
     "tt_table_prefault",
+    "tt_topk_mips",
 ]
 
 _lib = None

@@ -60,6 +60,7 @@ int tt_abi_version(void) { return TT_ABI_VERSION; }
 // tt_peer_exchange
 // tt_kjt_admit
 // tt_table_prefault
-int tt_num_entry_points(void) { return 53; }
+// tt_topk_mips
+int tt_num_entry_points(void) { return 54; }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-"""Checkpoint, evaluation and embedding export around the fused steps (SURVEY.md section 8(f) rows
-2-4), in the reference's formats.
+"""Checkpoint, evaluation, embedding export and retrieval evaluation around the fused steps
+(SURVEY.md section 8(f) rows 2-4), in the reference's formats.
 
 * Checkpoint (03_model_training.py:474-502 writes, :1015-1054 reads): the gathered state dict of
   ``TwoTowerTrainTask`` — keys ``two_tower.ebc.embedding_bags.t_<feature>.weight`` (full tables,
@@ -14,6 +14,10 @@
 * Embedding export (03:1056-1122, :1160-1240): every row of a table through its tower (EBC of a
   one-id bag = the row itself, then the MLP with ReLU on every layer); row i is labelled id i + 1
   as the reference does (:1168, :1235), which is NOT the training map id -> id % N (03:361).
+* Retrieval evaluation (04_evaluate_retrieval.py:125-153, :202-226): the top k items of every test
+  user, exactly (ops.topk_mips instead of a vector index), by the model's dot product or by L2 as
+  the reference's index ranks, and recall@k / precision@k / nDCG@k against a jagged ground truth
+  (metrics.retrieval_metrics).
 """
 from __future__ import annotations
 
@@ -151,3 +155,67 @@ def export_fused(step, tower: str = "candidate", **kw) -> Tuple[torch.Tensor, to
     t = 1 if tower == "candidate" else 0
     towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
     return export_embeddings(step.tables.table_view(t), towers[t], **kw)
+
+
+# ---- retrieval evaluation (04_evaluate_retrieval.py) ---------------------------------------------
+
+
+def l2_bias(item_emb: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
+    """bias[n] = -0.5 |c_n|^2 of the bf16-rounded rows (what the kernel multiplies), fp32: with it
+    the inner-product order is the ascending-L2 order, |q - c|^2 = |q|^2 - 2 (q.c - 0.5 |c|^2)."""
+    out = torch.empty(item_emb.shape[0], dtype=torch.float32, device=item_emb.device)
+    for lo in range(0, item_emb.shape[0], chunk):
+        c = item_emb[lo:lo + chunk].to(torch.bfloat16).to(torch.float64)
+        out[lo:lo + chunk] = (-0.5 * (c * c).sum(1)).to(torch.float32)
+    return out
+
+
+def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metric: str = "dot",
+             query_chunk: int = 1 << 16, bias: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The query loop of 04_evaluate_retrieval.py:131-153 without an index: for each row of
+    ``user_emb`` the exact top ``k`` rows of ``item_emb`` (ops.topk_mips), ``query_chunk`` queries per
+    launch. ``metric``: "dot" (the model's own score) or "l2" (the order of the reference's vector
+    index; ``bias`` = l2_bias(item_emb), computed here when not passed). Returns (ids [M, k] int64
+    in the reference's labels — row i is id i + 1, as export_embeddings; 0 past the table —, scores
+    [M, k] fp32: q.c, or q.c - 0.5 |c|^2 for "l2")."""
+    if metric not in ("dot", "l2"):
+        raise ValueError("metric must be 'dot' or 'l2'")
+    if metric == "l2" and bias is None:
+        bias = l2_bias(item_emb)
+    if metric == "dot":
+        bias = None
+    M = user_emb.shape[0]
+    ids = torch.empty(M, k, dtype=torch.int64, device=user_emb.device)
+    scores = torch.empty(M, k, dtype=torch.float32, device=user_emb.device)
+    for lo in range(0, M, query_chunk):
+        i, s = ops.topk_mips(user_emb[lo:lo + query_chunk], item_emb, k, bias=bias)
+        ids[lo:lo + query_chunk] = i + 1
+        scores[lo:lo + query_chunk] = s
+    return ids, scores
+
+
+def retrieve_fused(step, user_rows: torch.Tensor, k: int = 100, metric: str = "dot",
+                   item_emb: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """retrieve() for a FusedTwoTowerStep: rows ``user_rows`` (int64 row indices) of the user table
+    through the query tower (as export does), against the item table through the candidate tower
+    (export_fused, unless its embeddings ``item_emb`` are passed in)."""
+    towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
+    x = step.tables.table_view(0)[user_rows.to(step.device)]
+    for w, b in towers[0]:
+        x = ops.linear_fwd([x], [w.contiguous()], [b], relu=True)[0]
+    if item_emb is None:
+        item_emb = export_fused(step, "candidate")[1]
+    return retrieve(x, item_emb, k=k, metric=metric)
+
+
+def evaluate_retrieval(step, user_rows: torch.Tensor, target_values: torch.Tensor, target_offsets: torch.Tensor,
+                       k: int = 100, metric: str = "dot", item_emb: Optional[torch.Tensor] = None) -> Dict[str, object]:
+    """Retrieval evaluation of 04_evaluate_retrieval.py:202-226 (mlflow.evaluate, model_type
+    "retriever"): the top ``k`` item ids of every user row against its jagged ground truth
+    (``target_values`` item ids in the reference's labels, ``target_offsets`` [M + 1]);
+    metrics.retrieval_metrics' dict."""
+    from .metrics import retrieval_metrics
+
+    ids, _ = retrieve_fused(step, user_rows, k=k, metric=metric, item_emb=item_emb)
+    ids = torch.where(ids > 0, ids, torch.full_like(ids, -1))  # padding (label 0) is no id
+    return retrieval_metrics(ids, target_values.to(ids.device), target_offsets.to(ids.device), k)

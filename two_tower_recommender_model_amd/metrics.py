@@ -1,4 +1,7 @@
-"""Binary AUROC on device — the metric the reference's evaluate() computes with
+"""Evaluation metrics on device: binary AUROC (below) and the retrieval metrics of
+04_evaluate_retrieval.py (``retrieval_metrics``, at the end).
+
+Binary AUROC — the metric the reference's evaluate() computes with
 ``torchmetrics.AUROC(task="binary")`` (03_model_training.py:524, :545-551; torchmetrics is not part
 of this image). ``install_torchmetrics_alias()`` exposes it as ``torchmetrics.AUROC`` so the
 reference's evaluate() runs unchanged.
@@ -114,3 +117,52 @@ def install_torchmetrics_alias() -> Optional[types.ModuleType]:
         mod.__doc__ = "two_tower_recommender_model_amd stand-in: binary AUROC only"
         sys.modules["torchmetrics"] = mod
         return mod
+
+
+def retrieval_metrics(pred_ids: torch.Tensor, target_values: torch.Tensor, target_offsets: torch.Tensor, k: int):
+    """recall@k, precision@k and nDCG@k of retrieved id lists against a jagged ground truth — what
+    the reference's evaluator (mlflow.evaluate, model_type="retriever", 04_evaluate_retrieval.py:
+    202-226) reports with binary relevance. ``pred_ids`` [M, >= k]: each query's ids in rank order,
+    -1 = no id (padding); only the first ``k`` columns count. Query m's relevant ids are
+    ``target_values[target_offsets[m]:target_offsets[m + 1]]`` (distinct). Per query:
+    hits = |retrieved ∩ relevant| over the valid retrieved ids; recall = hits / |relevant|;
+    precision = hits / (valid retrieved ids) (0 when none); nDCG = DCG / IDCG with gain 1, discount
+    log2(rank + 1), IDCG over min(|relevant|, k) ranks. Queries with an empty relevant set are left
+    out of the means (and counted in "empty_queries"; their per-query values are nan).
+    Returns {"recall_at_k", "precision_at_k", "ndcg_at_k" (means, floats), "per_query": {the three
+    [M] float64 tensors}, "queries", "empty_queries", "k"}. Plain torch, any device."""
+    pred = pred_ids[:, :k].to(torch.int64)
+    M, kk = pred.shape
+    dev = pred.device
+    offs = target_offsets.to(torch.int64).to(dev)
+    vals = target_values.to(torch.int64).to(dev)
+    nrel = offs[1:] - offs[:-1]
+    valid = pred >= 0
+    owner = torch.repeat_interleave(torch.arange(M, device=dev), nrel)
+    hit = torch.zeros(M, kk, dtype=torch.bool, device=dev)
+    if vals.numel():
+        # sorted (query, id) codes of the ground truth; a retrieved id hits when its code is there
+        base = int(max(int(vals.max()), int(pred.max()) if pred.numel() else 0, 0)) + 2
+        codes = torch.sort(owner * base + vals).values
+        q = torch.arange(M, device=dev).unsqueeze(1) * base + pred.clamp(min=0)
+        pos = torch.searchsorted(codes, q.reshape(-1)).clamp(max=codes.numel() - 1).view(M, kk)
+        hit = (codes[pos] == q) & valid
+    hits = hit.sum(1).to(torch.float64)
+    nvalid = valid.sum(1).to(torch.float64)
+    disc = 1.0 / torch.log2(torch.arange(2, kk + 2, dtype=torch.float64, device=dev))
+    dcg = (hit.to(torch.float64) * disc).sum(1)
+    cum = torch.cat([torch.zeros(1, dtype=torch.float64, device=dev), torch.cumsum(disc, 0)])
+    idcg = cum[nrel.clamp(max=kk)]
+    nonempty = nrel > 0
+    nan = torch.full((M,), float("nan"), dtype=torch.float64, device=dev)
+    recall = torch.where(nonempty, hits / nrel.clamp(min=1).to(torch.float64), nan)
+    precision = torch.where(nonempty, hits / nvalid.clamp(min=1), nan)
+    ndcg = torch.where(nonempty, dcg / idcg.clamp(min=1e-300), nan)
+    n = int(nonempty.sum())
+
+    def mean(x):
+        return float(x[nonempty].sum() / n) if n else float("nan")
+
+    return {"recall_at_k": mean(recall), "precision_at_k": mean(precision), "ndcg_at_k": mean(ndcg),
+            "per_query": {"recall_at_k": recall, "precision_at_k": precision, "ndcg_at_k": ndcg},
+            "queries": n, "empty_queries": M - n, "k": k}

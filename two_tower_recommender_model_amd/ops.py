@@ -873,3 +873,34 @@ class FusedTowers:
                                       float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
                                       ptr(step_state), 1 if do_adam else 0, ptr(grads_out), ptr(self.ws),
                                       self.nbytes, stream_handle(self.device)), "tower_update")
+
+
+# ---- retrieval ---------------------------------------------------------------------------------
+
+
+def topk_mips(queries: torch.Tensor, items: torch.Tensor, k: int, bias: Optional[torch.Tensor] = None,
+              splits: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Exact top-k by inner product (tt_topk_mips; the vector-index query of
+    04_evaluate_retrieval.py:131-153): for each row of ``queries`` [M, E] the ``k`` rows of ``items``
+    [N, E] of highest score q.c (+ ``bias`` [N] fp32), fp32 or bf16 operands (fp32 is rounded to bf16
+    on load; rows may be strided, the last dimension contiguous), fp32 accumulation. Returns (ids
+    [M, k] int64 row indices — -1 past N —, scores [M, k] fp32), each list sorted by higher score,
+    then lower index; bit-identical for any ``splits`` (None: chosen by the library; 1..64)."""
+    _dev(queries, items, bias)
+    if queries.dim() != 2 or items.dim() != 2 or queries.shape[1] != items.shape[1] or \
+            queries.stride(1) != 1 or items.stride(1) != 1:
+        raise _lib.TTError("topk_mips: queries [M, E] and items [N, E], last dimension contiguous")
+    M, E = queries.shape
+    N = items.shape[0]
+    dev = queries.device
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous()):
+        raise _lib.TTError("topk_mips: bias must be contiguous fp32 [N]")
+    S = 0 if splits is None else int(splits)
+    lib = _lib_()
+    ids = torch.empty(M, k, dtype=torch.int64, device=dev)
+    scores = torch.empty(M, k, dtype=torch.float32, device=dev)
+    ws = scratch(lib.tt_topk_mips_workspace_bytes(M, N, k, S), dev, "topk_mips")
+    check(lib.tt_topk_mips(ptr(queries), _x_code(queries), queries.stride(0), ptr(items), _x_code(items),
+                           items.stride(0), ptr(bias), M, N, E, k, S, ptr(ids), ptr(scores), ptr(ws), ws.numel(),
+                           stream_handle(dev)), "topk_mips")
+    return ids, scores
