@@ -42,6 +42,8 @@
  *                                 Adam step (03:826-829), as three fused kernels
  *   tt_topk_mips               <- the vector-index query loop of 04_evaluate_retrieval.py:131-153
  *                                 (exact top-k by inner product over the exported item embeddings)
+ *   tt_topk_mips_filtered      <- the same query with the index's `filters=` (04:100, an item mask
+ *                                 shared by all queries) and each user's seen items excluded
  *   tt_launch (a launch plan)  <- the same backward work with several roles in one launch: the
  *                                 weight gradients beside the embedding update / next-batch insert /
  *                                 shard route and gather ("launch plans" below)
@@ -617,6 +619,32 @@ size_t tt_topk_mips_workspace_bytes(int64_t M, int64_t N, int k, int splits);
 int tt_topk_mips(const void* queries, int q_dtype, int64_t ldq, const void* items, int c_dtype, int64_t ldc,
                  const float* bias, int64_t M, int64_t N, int E, int k, int splits, int64_t* ids, float* scores,
                  void* workspace, size_t ws_bytes, void* stream);
+
+/* tt_topk_mips over each query's ELIGIBLE items (ABI 4 addition): the item restriction the reference
+ * hands its vector index (`filters=` of the query at 04_evaluate_retrieval.py:100, shared by all
+ * queries) and the per-user exclusion of already-seen items (the train / validate positives of the
+ * 80/10/10 split, 02_feature_engineering.py:93-114, which otherwise fill the top of a user's list
+ * ahead of the held-out ground truth). Everything tt_topk_mips documents holds unchanged: operands,
+ * strides, rounding, the score chain, the total order, the limits, `splits`, two launches, no
+ * allocation, no synchronisation; the workspace is tt_topk_mips_workspace_bytes.
+ *   allow: NULL (every item) or ceil(N / 32) words: item n is eligible for every query iff bit
+ *     n & 31 of word n >> 5 is set. Bits at positions >= N of the last word are ignored.
+ *   excl_values / excl_offsets: both NULL or both given (TT_EINVAL otherwise). Query m is also denied
+ *     the item indices excl_values[excl_offsets[m] .. excl_offsets[m + 1]). excl_offsets has M + 1
+ *     non-decreasing entries, absolute into excl_values (they need not start at 0: a chunk of the
+ *     queries is served by a view of the offsets). Each query's segment is ascending; duplicates are
+ *     allowed; values outside [0, N) match nothing. An unsorted segment gives an unspecified
+ *     selection; only the segment is ever read.
+ * The result is exactly tt_topk_mips' for the query over its eligible items alone: the same score
+ * bits for the same pairs, the same order, ids are row indices into C; when fewer than k items are
+ * eligible the tail is id -1, score -inf; bit-identical across runs and split counts, and to
+ * tt_topk_mips when all three pointers are NULL. A denied item is never returned and never raises a
+ * query's threshold or displaces an eligible item. The mask is applied where candidates are decided;
+ * a query's list is searched (binary, one lane per key) when its candidate buffer is merged. */
+int tt_topk_mips_filtered(const void* queries, int q_dtype, int64_t ldq, const void* items, int c_dtype, int64_t ldc,
+                          const float* bias, int64_t M, int64_t N, int E, int k, int splits,
+                          const uint32_t* allow, const int32_t* excl_values, const int64_t* excl_offsets,
+                          int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream);
 
 /* SETUP ONLY (allocating, synchronising): device memory for embedding tables on the current
  * device, physically contiguous when the driver can give it (hipDeviceMallocContiguous: the largest

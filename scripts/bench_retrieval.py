@@ -6,6 +6,12 @@ device; nothing is read from outside the tree.
 
     python scripts/bench_retrieval.py                       # M 4096, N 4,194,304, E 64, k 100
     python scripts/bench_retrieval.py --M 10000 --N 100000000 --items bf16 --no-baseline --runs 1
+    python scripts/bench_retrieval.py --no-baseline --filter    # + the filtered arms, --seen 256
+
+--filter adds two arms of tt_topk_mips_filtered to the interleaved runs: ``filtered_noop`` (an
+all-ones item mask and empty exclusion lists: the price of the filtered kernel itself) and
+``filtered`` (a seeded mask with ~90 % ones and --seen seeded uniform item ids per query, sorted), and
+prints each one's ratio to ``fused`` of the same process.
 """
 import argparse
 import json
@@ -54,6 +60,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--splits", type=int, default=None)
     ap.add_argument("--no-baseline", action="store_true")
+    ap.add_argument("--filter", action="store_true", help="add the filtered_noop and filtered arms")
+    ap.add_argument("--seen", type=int, default=256, help="excluded ids per query of the filtered arm")
     a = ap.parse_args()
 
     dev = torch.device("cuda:0")
@@ -74,6 +82,14 @@ def main():
         return torch_arm(q16, c16, a.k, a.chunk)
 
     arms = {"fused": fused} if a.no_baseline else {"fused": fused, "torch": composed}
+    if a.filter:
+        ones = ops.pack_allow_mask(torch.ones(a.N, dtype=torch.bool, device=dev))
+        empty = (torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(a.M + 1, dtype=torch.int64, device=dev))
+        mask = ops.pack_allow_mask(torch.rand(a.N, device=dev, generator=g) < 0.9)
+        offs = torch.arange(a.M + 1, dtype=torch.int64, device=dev) * a.seen
+        seen = (ops.sort_exclusions(torch.randint(0, a.N, (a.M * a.seen,), device=dev, generator=g), offs, a.N), offs)
+        arms["filtered_noop"] = lambda: ops.topk_mips(q, c, a.k, splits=a.splits, allow=ones, exclude=empty)
+        arms["filtered"] = lambda: ops.topk_mips(q, c, a.k, splits=a.splits, allow=mask, exclude=seen)
     for _ in range(a.warmup):
         for fn in arms.values():
             fn()
@@ -93,6 +109,12 @@ def main():
                   "tflops": round(flop / med / 1e9, 1)}
     res["item_bytes"] = c.numel() * c.element_size()
     res["fused"]["item_stream_tb_s"] = round(res["item_bytes"] / res["fused"]["median_ms"] / 1e9, 3)
+    if a.filter:
+        res["seen"] = a.seen
+        for n in ("filtered_noop", "filtered"):
+            res[n]["ratio_to_fused"] = round(res[n]["median_ms"] / res["fused"]["median_ms"], 4)
+        res["filtered_noop"]["equals_fused"] = bool(torch.equal(outs["filtered_noop"][0], outs["fused"][0]) and
+                                                    torch.equal(outs["filtered_noop"][1], outs["fused"][1]))
     if not a.no_baseline:
         res["speedup_median"] = round(res["torch"]["median_ms"] / res["fused"]["median_ms"], 2)
         # slowest fused run against the fastest torch run: > 1 means faster by more than the spread

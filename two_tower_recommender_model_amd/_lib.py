@@ -328,6 +328,8 @@ SIGNATURES = {
     "tt_table_prefault": (_int, [_vp, _sz, _sz, _vp, _vp]),
     "tt_topk_mips_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "tt_topk_mips": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _sz, _vp]),
+    "tt_topk_mips_filtered": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp,
+                                     _vp, _vp, _vp, _sz, _vp]),
     "tt_table_alloc": (_int, [_sz, _pvp, C.POINTER(C.c_int)]),
     "tt_table_free": (_int, [_vp]),
 }
@@ -387,6 +389,7 @@ COMPUTE_ENTRY_POINTS = [
     "tt_kjt_admit",
     "tt_table_prefault",
     "tt_topk_mips",
+    "tt_topk_mips_filtered",
 ]
 
 _lib = None

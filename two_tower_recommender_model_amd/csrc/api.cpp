@@ -61,6 +61,7 @@ int tt_abi_version(void) { return TT_ABI_VERSION; }
 // tt_kjt_admit
 // tt_table_prefault
 // tt_topk_mips
-int tt_num_entry_points(void) { return 54; }
+// tt_topk_mips_filtered
+int tt_num_entry_points(void) { return 55; }
 
 }  // extern "C"

@@ -24,9 +24,19 @@
 // The score of a pair is the MFMA chain over E in ascending k-steps from a zero accumulator, then
 // + bias: a function of the two rows' bf16 values and bias[n] only, so the result (unique under the
 // total order) is bit-identical across runs, M, N and split counts.
+//
+// tt_topk_mips_filtered runs the FILT instantiations of the same kernel: the top k over each query's
+// ELIGIBLE items. The item mask shared by all queries (a bit per item) is staged per chunk beside the
+// bias and decides, with the threshold, what becomes a candidate. A query's exclusion list (ascending
+// item indices) is tested where it is cheap: not per candidate, but when the query's candidate
+// buffer is about to be merged into its list (topk_drop_excluded: one lane per buffered key, a binary
+// search each). Thresholds rise only in a merge and the final flush merges too, so an excluded key
+// never raises a threshold, never enters a list and never displaces an eligible item; all it costs
+// is its place in the buffer until the next merge. The unfiltered instantiations are unchanged.
 #include "tt_common.h"
 
 #include <limits>
+#include <type_traits>
 
 namespace tt {
 
@@ -77,6 +87,15 @@ struct TopkArgs {
   u64* ws;  // [S][M][k] keys, each list sorted descending, 0 = no entry
   int64_t ldq, ldc, M, N, per;  // per: items per split (a multiple of the chunk)
   int k, S, qtiles, q_bf16, c_bf16, c_vec;
+};
+
+// the FILT instantiations' arguments: allow is NULL or ceil(N / 32) words (bit n & 31 of word n >> 5:
+// item n is eligible); excl_offsets is NULL or [M + 1] absolute offsets into excl_values, query m's
+// segment ascending
+struct TopkFiltArgs : TopkArgs {
+  const uint32_t* allow;
+  const int32_t* excl_values;
+  const int64_t* excl_offsets;
 };
 
 // one wave's selection state in LDS
@@ -135,13 +154,48 @@ __device__ __noinline__ void topk_merge_query(const WaveSel w, int q, u64* gl, i
   lds_wave_sync();
 }
 
-template <int KS, bool BIAS>
-__global__ void __launch_bounds__(TK_THREADS, 2) topk_mips_kernel(const TopkArgs a) {
+// wave-local query q's buffered candidates that are in the query's exclusion segment
+// xv[xo[0], xo[1]) (ascending; only the segment is read) are dropped and the buffer is compacted
+// (its order is free: the merge ranks by counting). One lane per buffered key (at most TK_CB = 32),
+// so the binary searches' dependent loads run side by side. Returns the candidates left.
+__device__ __noinline__ int topk_drop_excluded(const WaveSel w, int q, const int32_t* __restrict__ xv,
+                                               const int64_t* __restrict__ xo, int lane) {
+  const int nc = w.ccnt[q];
+  const int64_t beg = xo[0], end = xo[1];
+  if (end <= beg) return nc;
+  u64* cb = w.cbuf + q * TK_CB;
+  u64 e = 0ull;
+  bool keep = false;
+  if (lane < nc) {
+    e = cb[lane];
+    const int n = key_index(e);
+    int64_t lo = beg, hi = end;
+    while (lo < hi) {
+      const int64_t mid = lo + ((hi - lo) >> 1);
+      if (xv[mid] < n) lo = mid + 1; else hi = mid;
+    }
+    keep = !(lo < end && xv[lo] == n);
+  }
+  const u64 kept = __ballot(keep);
+  const int nk = __popcll(kept);
+  if (nk == nc) return nc;
+  lds_wave_sync();  // every lane has read its key
+  if (keep) cb[__popcll(kept & ((1ull << lane) - 1ull))] = e;  // places [0, nk)
+  if (lane >= nk && lane < TK_CB) cb[lane] = 0ull;
+  if (lane == 0) w.ccnt[q] = nk;
+  lds_wave_sync();
+  return nk;
+}
+
+template <int KS, bool BIAS, bool FILT>
+__global__ void __launch_bounds__(TK_THREADS, 2)
+    topk_mips_kernel(const std::conditional_t<FILT, TopkFiltArgs, TopkArgs> a) {
   constexpr int E = KS * 32, STRIDE = E + 8, GPR = E / 8;  // GPR: 8-element groups per item row
   constexpr int TK_IC = tk_chunk(E);
   constexpr int GPT = TK_IC * GPR / TK_THREADS;             // groups per thread
   __shared__ __attribute__((aligned(16))) __bf16 items[2][TK_IC * STRIDE];
-  __shared__ __attribute__((aligned(16))) float bias_s[2][TK_IC];
+  // FILT: the chunk's TK_IC / 32 mask words follow its bias
+  __shared__ __attribute__((aligned(16))) float bias_s[2][TK_IC + (FILT ? TK_IC / 32 : 0)];
   __shared__ u64 cbuf_s[TK_WAVES][TK_QW * TK_CB];
   __shared__ u64 lscr_s[TK_WAVES][TT_TOPK_MAX_K];
   __shared__ int ccnt_s[TK_WAVES][TK_QW];
@@ -165,6 +219,15 @@ __global__ void __launch_bounds__(TK_THREADS, 2) topk_mips_kernel(const TopkArgs
     w.ccnt[lane] = 0;
     w.lcnt[lane] = 0;
     w.thrs[lane] = m_wave + lane < a.M ? -std::numeric_limits<float>::infinity() : std::numeric_limits<float>::infinity();
+  }
+  // FILT: does any of the wave's queries have a non-empty exclusion segment (offsets never decrease)?
+  // Where none has, the merges go as in the unfiltered kernel, without the look at the offsets
+  bool wave_excl = false;
+  if constexpr (FILT) {
+    if (a.excl_offsets && m_wave < a.M) {
+      const int64_t m_last = m_wave + TK_QW < a.M ? m_wave + TK_QW : a.M;
+      wave_excl = __builtin_amdgcn_readfirstlane((int)(a.excl_offsets[m_last] > a.excl_offsets[m_wave])) != 0;
+    }
   }
 
   // the wave's queries as B operands: lane l holds query (l & 15), k = 32 ks + 8 (l >> 4) + j
@@ -197,6 +260,7 @@ __global__ void __launch_bounds__(TK_THREADS, 2) topk_mips_kernel(const TopkArgs
   f32x4 rawf[GPT][2];
   bf16x8 rawb[GPT];
   float rawbias = 0.f;
+  uint32_t rawmask = 0u;
   auto load_chunk = [&](int c) {
     const int64_t n0 = n_beg + (int64_t)c * TK_IC;
 #pragma unroll
@@ -227,6 +291,13 @@ __global__ void __launch_bounds__(TK_THREADS, 2) topk_mips_kernel(const TopkArgs
       }
     }
     if (BIAS && tid < TK_IC) rawbias = n0 + tid < n_end ? a.bias[n0 + tid] : 0.f;
+    if constexpr (FILT) {
+      // n0 is a multiple of the chunk, the chunk of 32: the chunk's words are whole
+      if (tid < TK_IC / 32) {
+        const int64_t wd = (n0 >> 5) + tid;
+        rawmask = !a.allow ? 0xffffffffu : wd < ((a.N + 31) >> 5) ? a.allow[wd] : 0u;
+      }
+    }
   };
   auto store_chunk = [&](int buf) {
 #pragma unroll
@@ -243,6 +314,9 @@ __global__ void __launch_bounds__(TK_THREADS, 2) topk_mips_kernel(const TopkArgs
       *reinterpret_cast<bf16x8*>(&items[buf][row * STRIDE + kc]) = o;
     }
     if (BIAS && tid < TK_IC) bias_s[buf][tid] = rawbias;
+    if constexpr (FILT) {
+      if (tid < TK_IC / 32) *reinterpret_cast<uint32_t*>(&bias_s[buf][TK_IC + tid]) = rawmask;
+    }
   };
 
   if (nchunks > 0) {
@@ -263,6 +337,10 @@ __global__ void __launch_bounds__(TK_THREADS, 2) topk_mips_kernel(const TopkArgs
         af[ks] = *reinterpret_cast<const bf16x8*>(&items[buf][(it * 16 + (lane & 15)) * STRIDE + ks * 32 + (lane >> 4) * 8]);
       f32x4 bv = (f32x4)(0.f);
       if (BIAS) bv = *reinterpret_cast<const f32x4*>(&bias_s[buf][it * 16 + (lane >> 4) * 4]);
+      // FILT: the chunk's mask word it >> 1, read with the tile's other LDS reads: not one more
+      // latency inside the candidate branch
+      uint32_t mword = 0u;
+      if constexpr (FILT) mword = *reinterpret_cast<const uint32_t*>(&bias_s[buf][TK_IC + (it >> 1)]);
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
         f32x4 acc = (f32x4)(0.f);
@@ -276,9 +354,19 @@ __global__ void __launch_bounds__(TK_THREADS, 2) topk_mips_kernel(const TopkArgs
           const int64_t nb = n0 + it * 16 + (lane >> 4) * 4;
           bool pass[4];
           int cnt = 0;
+          // FILT: the lane's 4 items are bits (it & 1) * 16 + (lane >> 4) * 4 + r of the word. The
+          // empty asm keeps the shift and the bit tests here: the compiler otherwise hoists them
+          // (9 VALU instructions) into every tile, candidates or not
+          uint32_t mbits = 0xfu;
+          if constexpr (FILT) {
+            uint32_t mw = mword;
+            asm volatile("" : "+v"(mw));
+            mbits = mw >> ((it & 1) * 16 + (lane >> 4) * 4);
+          }
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             pass[r] = acc[r] > thr[qt] && nb + r < n_end;
+            if constexpr (FILT) pass[r] = pass[r] && ((mbits >> r) & 1u);
             cnt += pass[r] ? 1 : 0;
           }
           // the tile's candidates per query (its 4 lanes l, l ^ 16, l ^ 32, l ^ 48: at most 16) and
@@ -294,6 +382,10 @@ __global__ void __launch_bounds__(TK_THREADS, 2) topk_mips_kernel(const TopkArgs
           while (need) {
             const int qi = qt * 16 + __builtin_ctzll(need);
             need &= need - 1;
+            if constexpr (FILT) {
+              if (wave_excl && topk_drop_excluded(w, qi, a.excl_values, a.excl_offsets + m_wave + qi, lane) == 0)
+                continue;  // nothing left to merge, and the buffer is empty
+            }
             topk_merge_query(w, qi, a.ws + ((int64_t)split * a.M + m_wave + qi) * k, k, lane);
           }
           if (merged) base = w.ccnt[q];
@@ -316,6 +408,9 @@ __global__ void __launch_bounds__(TK_THREADS, 2) topk_mips_kernel(const TopkArgs
   for (int q = 0; q < TK_QW; ++q) {
     if (m_wave + q >= a.M) break;
     u64* gl = a.ws + ((int64_t)split * a.M + m_wave + q) * k;
+    if constexpr (FILT) {
+      if (w.ccnt[q] > 0 && wave_excl) topk_drop_excluded(w, q, a.excl_values, a.excl_offsets + m_wave + q, lane);
+    }
     if (w.ccnt[q] > 0) topk_merge_query(w, q, gl, k, lane);
     for (int i = w.lcnt[q] + lane; i < k; i += 64) gl[i] = 0ull;
   }
@@ -367,41 +462,47 @@ static const char* topk_check(int64_t M, int64_t N, int k, int splits) {
   return nullptr;
 }
 
-template <int KS>
-static void topk_launch(const TopkArgs& a, int blocks, hipStream_t st) {
+template <int KS, bool FILT>
+static void topk_launch(const TopkFiltArgs& a, int blocks, hipStream_t st) {
+  const std::conditional_t<FILT, TopkFiltArgs, TopkArgs>& ka = a;
   if (a.bias)
-    hipLaunchKernelGGL((topk_mips_kernel<KS, true>), dim3(blocks), dim3(TK_THREADS), 0, st, a);
+    hipLaunchKernelGGL((topk_mips_kernel<KS, true, FILT>), dim3(blocks), dim3(TK_THREADS), 0, st, ka);
   else
-    hipLaunchKernelGGL((topk_mips_kernel<KS, false>), dim3(blocks), dim3(TK_THREADS), 0, st, a);
+    hipLaunchKernelGGL((topk_mips_kernel<KS, false, FILT>), dim3(blocks), dim3(TK_THREADS), 0, st, ka);
 }
 
-}  // namespace tt
-
-extern "C" {
-
-size_t tt_topk_mips_workspace_bytes(int64_t M, int64_t N, int k, int splits) {
-  if (tt::topk_check(M, N, k, splits)) return 0;
-  const int S = splits ? splits : tt::topk_auto_splits(M, N);
-  return (size_t)S * (size_t)M * (size_t)k * 8;
+template <bool FILT>
+static void topk_launch_e(const TopkFiltArgs& a, int E, int blocks, hipStream_t st) {
+  switch (E / 32) {
+    case 1: topk_launch<1, FILT>(a, blocks, st); break;
+    case 2: topk_launch<2, FILT>(a, blocks, st); break;
+    case 3: topk_launch<3, FILT>(a, blocks, st); break;
+    default: topk_launch<4, FILT>(a, blocks, st); break;
+  }
 }
 
-int tt_topk_mips(const void* queries, int q_dtype, int64_t ldq, const void* items, int c_dtype, int64_t ldc,
-                 const float* bias, int64_t M, int64_t N, int E, int k, int splits, int64_t* ids, float* scores,
-                 void* workspace, size_t ws_bytes, void* stream) {
-  using namespace tt;
-  if (E < 32 || E > 128 || (E & 31)) return fail(TT_EINVAL, "tt_topk_mips: E must be a multiple of 32 in [32, 128]");
-  if (const char* msg = topk_check(M, N, k, splits)) return fail(TT_EINVAL, std::string("tt_topk_mips: ") + msg);
+// both entry points: `fn_name` prefixes the messages, `fn_merge` names the second launch; the FILT
+// kernel runs when a filter is given
+static int topk_run(const char* fn_name, const char* fn_merge, const void* queries, int q_dtype, int64_t ldq,
+                    const void* items, int c_dtype, int64_t ldc, const float* bias, int64_t M, int64_t N, int E, int k,
+                    int splits, const uint32_t* allow, const int32_t* excl_values, const int64_t* excl_offsets,
+                    int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream) {
+  const auto fn = [fn_name] { return std::string(fn_name); };  // built for a message only
+  if (E < 32 || E > 128 || (E & 31)) return fail(TT_EINVAL, fn() + ": E must be a multiple of 32 in [32, 128]");
+  if (const char* msg = topk_check(M, N, k, splits)) return fail(TT_EINVAL, fn() + ": " + msg);
   if ((q_dtype != TT_F32 && q_dtype != TT_BF16) || (c_dtype != TT_F32 && c_dtype != TT_BF16))
-    return fail(TT_EINVAL, "tt_topk_mips: q_dtype / c_dtype must be TT_F32 or TT_BF16");
-  if (ldq < E || ldc < E) return fail(TT_EINVAL, "tt_topk_mips: ldq / ldc must be >= E");
+    return fail(TT_EINVAL, fn() + ": q_dtype / c_dtype must be TT_F32 or TT_BF16");
+  if (ldq < E || ldc < E) return fail(TT_EINVAL, fn() + ": ldq / ldc must be >= E");
   if (!queries || !items || !ids || !scores || !workspace)
-    return fail(TT_EINVAL, "tt_topk_mips: null queries / items / ids / scores / workspace");
+    return fail(TT_EINVAL, fn() + ": null queries / items / ids / scores / workspace");
+  if ((excl_values == nullptr) != (excl_offsets == nullptr))
+    return fail(TT_EINVAL, fn() + ": excl_values and excl_offsets must both be NULL or both be given");
   const int S = splits ? splits : topk_auto_splits(M, N);
   if (ws_bytes < (size_t)S * (size_t)M * (size_t)k * 8)
-    return fail(TT_EINVAL, "tt_topk_mips: ws_bytes is smaller than tt_topk_mips_workspace_bytes");
+    return fail(TT_EINVAL, fn() + ": ws_bytes is smaller than tt_topk_mips_workspace_bytes");
   const int64_t qtiles = ceil_div(M, TK_QB);
 
-  TopkArgs a{};
+  TopkFiltArgs a{};
   a.q = queries;
   a.c = items;
   a.bias = bias;
@@ -418,18 +519,44 @@ int tt_topk_mips(const void* queries, int q_dtype, int64_t ldq, const void* item
   a.c_bf16 = c_dtype == TT_BF16;
   // 16-B loads of an item row's 8-element groups need the base and the row stride aligned
   a.c_vec = (reinterpret_cast<uintptr_t>(items) & 15) == 0 && (ldc % (a.c_bf16 ? 8 : 4)) == 0;
+  a.allow = allow;
+  a.excl_values = excl_values;
+  a.excl_offsets = excl_offsets;
   const int blocks = (int)(qtiles * S);
   hipStream_t st = as_stream(stream);
-  switch (E / 32) {
-    case 1: topk_launch<1>(a, blocks, st); break;
-    case 2: topk_launch<2>(a, blocks, st); break;
-    case 3: topk_launch<3>(a, blocks, st); break;
-    default: topk_launch<4>(a, blocks, st); break;
-  }
-  if (int rc = check_launch("tt_topk_mips")) return rc;
+  if (allow || excl_offsets)
+    topk_launch_e<true>(a, E, blocks, st);
+  else
+    topk_launch_e<false>(a, E, blocks, st);
+  if (int rc = check_launch(fn_name)) return rc;
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)ceil_div(M, TK_WAVES)), dim3(TK_THREADS), 0, st, a.ws, M, k, S,
                      ids, scores);
-  return check_launch("tt_topk_mips merge");
+  return check_launch(fn_merge);
+}
+
+}  // namespace tt
+
+extern "C" {
+
+size_t tt_topk_mips_workspace_bytes(int64_t M, int64_t N, int k, int splits) {
+  if (tt::topk_check(M, N, k, splits)) return 0;
+  const int S = splits ? splits : tt::topk_auto_splits(M, N);
+  return (size_t)S * (size_t)M * (size_t)k * 8;
+}
+
+int tt_topk_mips(const void* queries, int q_dtype, int64_t ldq, const void* items, int c_dtype, int64_t ldc,
+                 const float* bias, int64_t M, int64_t N, int E, int k, int splits, int64_t* ids, float* scores,
+                 void* workspace, size_t ws_bytes, void* stream) {
+  return tt::topk_run("tt_topk_mips", "tt_topk_mips merge", queries, q_dtype, ldq, items, c_dtype, ldc, bias, M, N, E, k,
+                      splits, nullptr, nullptr, nullptr, ids, scores, workspace, ws_bytes, stream);
+}
+
+int tt_topk_mips_filtered(const void* queries, int q_dtype, int64_t ldq, const void* items, int c_dtype, int64_t ldc,
+                          const float* bias, int64_t M, int64_t N, int E, int k, int splits, const uint32_t* allow,
+                          const int32_t* excl_values, const int64_t* excl_offsets, int64_t* ids, float* scores,
+                          void* workspace, size_t ws_bytes, void* stream) {
+  return tt::topk_run("tt_topk_mips_filtered", "tt_topk_mips_filtered merge", queries, q_dtype, ldq, items, c_dtype, ldc,
+                      bias, M, N, E, k, splits, allow, excl_values, excl_offsets, ids, scores, workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

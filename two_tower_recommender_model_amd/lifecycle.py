@@ -170,14 +170,45 @@ def l2_bias(item_emb: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
     return out
 
 
+def _retrieval_filters(N: int, M: int, device, allow, seen_values, seen_offsets):
+    """(packed allow words or None, (sorted int32 item rows, int64 offsets [M + 1]) or None) of
+    retrieve()'s filter arguments, on ``device``."""
+    if allow is not None:
+        allow = allow.to(device)
+        if allow.dtype == torch.bool:
+            if allow.numel() != N:
+                raise ValueError("allow must be bool [N] over the item rows, or the packed int32 words")
+            allow = ops.pack_allow_mask(allow)
+    if (seen_values is None) != (seen_offsets is None):
+        raise ValueError("seen_values and seen_offsets go together")
+    if seen_values is None:
+        return allow, None
+    if seen_offsets.numel() != M + 1:
+        raise ValueError("seen_offsets must have M + 1 entries")
+    offsets = seen_offsets.to(device=device, dtype=torch.int64).contiguous()
+    # label i + 1 is row i; a label outside 1..N is a row outside [0, N), which sort_exclusions
+    # turns into "no item"
+    rows = ops.sort_exclusions(seen_values.to(device=device, dtype=torch.int64) - 1, offsets, N)
+    return allow, (rows, offsets)
+
+
 def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metric: str = "dot",
-             query_chunk: int = 1 << 16, bias: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             query_chunk: int = 1 << 16, bias: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
+             seen_values: Optional[torch.Tensor] = None,
+             seen_offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The query loop of 04_evaluate_retrieval.py:131-153 without an index: for each row of
     ``user_emb`` the exact top ``k`` rows of ``item_emb`` (ops.topk_mips), ``query_chunk`` queries per
     launch. ``metric``: "dot" (the model's own score) or "l2" (the order of the reference's vector
     index; ``bias`` = l2_bias(item_emb), computed here when not passed). Returns (ids [M, k] int64
     in the reference's labels — row i is id i + 1, as export_embeddings; 0 past the table —, scores
-    [M, k] fp32: q.c, or q.c - 0.5 |c|^2 for "l2")."""
+    [M, k] fp32: q.c, or q.c - 0.5 |c|^2 for "l2").
+
+    Filters (tt_topk_mips_filtered; all None: the unfiltered call): ``allow`` restricts the catalogue
+    for every query (bool [N] over the item rows, or ops.pack_allow_mask's words: the index's
+    ``filters=`` of 04_evaluate_retrieval.py:100); ``seen_values`` / ``seen_offsets`` [M + 1] are each
+    user's already-seen items (jagged, in the reference's labels as ``target_values``; labels outside
+    1..N are dropped), never returned to that user. The lists are sorted once; a chunk of queries
+    takes a view of the offsets."""
     if metric not in ("dot", "l2"):
         raise ValueError("metric must be 'dot' or 'l2'")
     if metric == "l2" and bias is None:
@@ -185,37 +216,49 @@ def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metri
     if metric == "dot":
         bias = None
     M = user_emb.shape[0]
+    allow, seen = _retrieval_filters(item_emb.shape[0], M, user_emb.device, allow, seen_values, seen_offsets)
     ids = torch.empty(M, k, dtype=torch.int64, device=user_emb.device)
     scores = torch.empty(M, k, dtype=torch.float32, device=user_emb.device)
     for lo in range(0, M, query_chunk):
-        i, s = ops.topk_mips(user_emb[lo:lo + query_chunk], item_emb, k, bias=bias)
+        n = min(query_chunk, M - lo)
+        exclude = None if seen is None else (seen[0], seen[1][lo:lo + n + 1])
+        i, s = ops.topk_mips(user_emb[lo:lo + n], item_emb, k, bias=bias, allow=allow, exclude=exclude)
         ids[lo:lo + query_chunk] = i + 1
         scores[lo:lo + query_chunk] = s
     return ids, scores
 
 
 def retrieve_fused(step, user_rows: torch.Tensor, k: int = 100, metric: str = "dot",
-                   item_emb: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                   item_emb: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
+                   seen_values: Optional[torch.Tensor] = None, seen_offsets: Optional[torch.Tensor] = None,
+                   query_chunk: int = 1 << 16) -> Tuple[torch.Tensor, torch.Tensor]:
     """retrieve() for a FusedTwoTowerStep: rows ``user_rows`` (int64 row indices) of the user table
     through the query tower (as export does), against the item table through the candidate tower
-    (export_fused, unless its embeddings ``item_emb`` are passed in)."""
+    (export_fused, unless its embeddings ``item_emb`` are passed in). ``allow``, ``seen_values`` /
+    ``seen_offsets`` and ``query_chunk`` as retrieve()."""
     towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
     x = step.tables.table_view(0)[user_rows.to(step.device)]
     for w, b in towers[0]:
         x = ops.linear_fwd([x], [w.contiguous()], [b], relu=True)[0]
     if item_emb is None:
         item_emb = export_fused(step, "candidate")[1]
-    return retrieve(x, item_emb, k=k, metric=metric)
+    return retrieve(x, item_emb, k=k, metric=metric, query_chunk=query_chunk, allow=allow, seen_values=seen_values,
+                    seen_offsets=seen_offsets)
 
 
 def evaluate_retrieval(step, user_rows: torch.Tensor, target_values: torch.Tensor, target_offsets: torch.Tensor,
-                       k: int = 100, metric: str = "dot", item_emb: Optional[torch.Tensor] = None) -> Dict[str, object]:
+                       k: int = 100, metric: str = "dot", item_emb: Optional[torch.Tensor] = None,
+                       allow: Optional[torch.Tensor] = None, seen_values: Optional[torch.Tensor] = None,
+                       seen_offsets: Optional[torch.Tensor] = None, query_chunk: int = 1 << 16) -> Dict[str, object]:
     """Retrieval evaluation of 04_evaluate_retrieval.py:202-226 (mlflow.evaluate, model_type
     "retriever"): the top ``k`` item ids of every user row against its jagged ground truth
     (``target_values`` item ids in the reference's labels, ``target_offsets`` [M + 1]);
-    metrics.retrieval_metrics' dict."""
+    metrics.retrieval_metrics' dict. ``allow`` and ``seen_values`` / ``seen_offsets`` as retrieve():
+    with each user's training positives as the seen set, the held-out items are ranked among the
+    items the user has not seen, which is the usual protocol."""
     from .metrics import retrieval_metrics
 
-    ids, _ = retrieve_fused(step, user_rows, k=k, metric=metric, item_emb=item_emb)
+    ids, _ = retrieve_fused(step, user_rows, k=k, metric=metric, item_emb=item_emb, allow=allow,
+                            seen_values=seen_values, seen_offsets=seen_offsets, query_chunk=query_chunk)
     ids = torch.where(ids > 0, ids, torch.full_like(ids, -1))  # padding (label 0) is no id
     return retrieval_metrics(ids, target_values.to(ids.device), target_offsets.to(ids.device), k)

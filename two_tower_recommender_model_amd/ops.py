@@ -878,15 +878,55 @@ class FusedTowers:
 # ---- retrieval ---------------------------------------------------------------------------------
 
 
+def pack_allow_mask(mask: torch.Tensor) -> torch.Tensor:
+    """bool [N] -> the packed item mask of tt_topk_mips_filtered: int32 [ceil(N / 32)], bit n & 31 of
+    word n >> 5 = mask[n], the last word's bits past N zero. On the mask's device, no host sync."""
+    if mask.dim() != 1 or mask.dtype != torch.bool:
+        raise _lib.TTError("pack_allow_mask: mask must be bool [N]")
+    N = mask.numel()
+    W = (N + 31) // 32
+    bits = torch.zeros(W * 32, dtype=torch.int64, device=mask.device)
+    bits[:N] = mask
+    words = (bits.view(W, 32) << torch.arange(32, dtype=torch.int64, device=mask.device)).sum(1)
+    return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)  # the word's bits as int32
+
+
+def sort_exclusions(values: torch.Tensor, offsets: torch.Tensor, N: int) -> torch.Tensor:
+    """The exclusion lists of tt_topk_mips_filtered from unsorted ones: ``values`` (item indices, any
+    integer dtype) with each segment [offsets[m], offsets[m + 1]) ascending, int32; the offsets (any
+    start) stay as they are. A value outside [0, N) becomes N, which matches no item. One sort of
+    the codes owner * (N + 1) + value, on the values' device, no host sync."""
+    if values.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 1 or values.dtype.is_floating_point:
+        raise _lib.TTError("sort_exclusions: values [L] integer, offsets [M + 1]")
+    v = values.to(torch.int64)
+    v = torch.where((v >= 0) & (v < N), v, torch.full_like(v, N))
+    pos = torch.arange(v.numel(), dtype=torch.int64, device=v.device)
+    # a position's owner (-1 before the first segment, M past the last) never decreases, so the sorted
+    # codes' owners are the positions' owners
+    owner = torch.searchsorted(offsets.to(device=v.device, dtype=torch.int64).contiguous(), pos, right=True) - 1
+    codes = torch.sort(owner * (N + 1) + v).values
+    return (codes - owner * (N + 1)).to(torch.int32)
+
+
 def topk_mips(queries: torch.Tensor, items: torch.Tensor, k: int, bias: Optional[torch.Tensor] = None,
-              splits: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+              splits: Optional[int] = None, allow: Optional[torch.Tensor] = None,
+              exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Exact top-k by inner product (tt_topk_mips; the vector-index query of
     04_evaluate_retrieval.py:131-153): for each row of ``queries`` [M, E] the ``k`` rows of ``items``
     [N, E] of highest score q.c (+ ``bias`` [N] fp32), fp32 or bf16 operands (fp32 is rounded to bf16
     on load; rows may be strided, the last dimension contiguous), fp32 accumulation. Returns (ids
     [M, k] int64 row indices — -1 past N —, scores [M, k] fp32), each list sorted by higher score,
-    then lower index; bit-identical for any ``splits`` (None: chosen by the library; 1..64)."""
-    _dev(queries, items, bias)
+    then lower index; bit-identical for any ``splits`` (None: chosen by the library; 1..64).
+
+    ``allow`` (pack_allow_mask: int32 [ceil(N / 32)], an item is eligible iff its bit is set) and
+    ``exclude`` ((values int32 [L], offsets int64 [M + 1]): query m is denied the item indices
+    values[offsets[m]:offsets[m + 1]], ascending within a segment as sort_exclusions leaves them;
+    the offsets are absolute and must lie within ``values``) restrict each query to its eligible
+    items (tt_topk_mips_filtered): the same lists as over those items alone, -1 / -inf where fewer
+    than k are eligible. With both None this is the unfiltered call."""
+    _dev(queries, items, bias, allow)
+    if exclude is not None:
+        _dev(*exclude)
     if queries.dim() != 2 or items.dim() != 2 or queries.shape[1] != items.shape[1] or \
             queries.stride(1) != 1 or items.stride(1) != 1:
         raise _lib.TTError("topk_mips: queries [M, E] and items [N, E], last dimension contiguous")
@@ -899,8 +939,26 @@ def topk_mips(queries: torch.Tensor, items: torch.Tensor, k: int, bias: Optional
     lib = _lib_()
     ids = torch.empty(M, k, dtype=torch.int64, device=dev)
     scores = torch.empty(M, k, dtype=torch.float32, device=dev)
+    if allow is not None and (allow.dtype != torch.int32 or allow.dim() != 1 or allow.numel() != (N + 31) // 32 or
+                              not allow.is_contiguous()):
+        raise _lib.TTError("topk_mips: allow must be contiguous int32 [ceil(N / 32)] (pack_allow_mask)")
+    xv = xo = None
+    if exclude is not None:
+        xv, xo = exclude
+        if xv.dtype != torch.int32 or xv.dim() != 1 or not xv.is_contiguous():
+            raise _lib.TTError("topk_mips: exclude values must be contiguous int32 [L]")
+        if xo.dtype != torch.int64 or xo.dim() != 1 or xo.numel() != M + 1 or not xo.is_contiguous():
+            raise _lib.TTError("topk_mips: exclude offsets must be contiguous int64 [M + 1]")
+        if xv.numel() == 0:  # no values: every segment is empty
+            xv = xo = None
     ws = scratch(lib.tt_topk_mips_workspace_bytes(M, N, k, S), dev, "topk_mips")
-    check(lib.tt_topk_mips(ptr(queries), _x_code(queries), queries.stride(0), ptr(items), _x_code(items),
-                           items.stride(0), ptr(bias), M, N, E, k, S, ptr(ids), ptr(scores), ptr(ws), ws.numel(),
-                           stream_handle(dev)), "topk_mips")
+    if allow is None and xv is None:
+        check(lib.tt_topk_mips(ptr(queries), _x_code(queries), queries.stride(0), ptr(items), _x_code(items),
+                               items.stride(0), ptr(bias), M, N, E, k, S, ptr(ids), ptr(scores), ptr(ws), ws.numel(),
+                               stream_handle(dev)), "topk_mips")
+    else:
+        check(lib.tt_topk_mips_filtered(ptr(queries), _x_code(queries), queries.stride(0), ptr(items), _x_code(items),
+                                        items.stride(0), ptr(bias), M, N, E, k, S, ptr(allow), ptr(xv), ptr(xo),
+                                        ptr(ids), ptr(scores), ptr(ws), ws.numel(), stream_handle(dev)),
+              "topk_mips_filtered")
     return ids, scores
