@@ -294,7 +294,8 @@ static size_t bwd_layout(void* base, int64_t L, BwdWs* w) {
   t.perm = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * L));
   t.urec = reinterpret_cast<URec*>(take(sizeof(URec) * L));
   t.lk = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * L));
-  t.ent_h = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * L));
+  t.ent_h = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * L));  // (the layout up to here is what
+  // tests/test_gpu_hash_adversary.py inspects: cnt, slot_of, lk and ent_h after tt_bwd_prepare[_cols])
   t.ent_c = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * L));
   t.ent_n = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * L));
   t.bsum_u = reinterpret_cast<int32_t*>(take(sizeof(int32_t) * nb));
