@@ -333,6 +333,39 @@ def test_sharded_pipelined_equals_synchronous(device, W):
         assert float(a.loss) == float(b.loss)
 
 
+def test_sharded_overlap_launch_u_equals_synchronous(device):
+    """overlap=True runs T2 on a side stream and launch U without it (tt_launch roles ROUTE_COUNT |
+    ADAGRAD). Bit for bit the synchronous step, whose route, row update and T2 are the single-role
+    exports the launch replaces (tt_shard_route_segs, tt_dedup_rowwise_adagrad, tt_tower_wgrad_pre):
+    the comparison of test_sharded_pipelined_equals_synchronous. Small id ranges: rows repeat."""
+    from two_tower_recommender_model_amd.sharded import FusedShardedTwoTowerStep, ThreadComm
+
+    B, D, N = 256, 64, [60, 90]
+    gen = torch.Generator().manual_seed(41)
+    full = [torch.empty(n, D).uniform_(-0.05, 0.05, generator=gen) for n in N]
+    pool = [([torch.randint(0, 2 * n, (B,), generator=gen).to(device) for n in N],
+             torch.randint(0, 2, (B,), generator=gen).to(torch.int32).to(device)) for _ in range(4)]
+    runs = {}
+    for mode in ("sync", "pipe"):
+        st = FusedShardedTwoTowerStep(ThreadComm.group(1)[0], N, D, [128, 64], B, device, full_tables=full, seed=8,
+                                      overlap=mode == "pipe")
+        if mode == "sync":
+            for i in range(6):
+                st.load_batch(*pool[i % 4])
+                st.step()
+        else:
+            assert st.overlap
+            st.run_eager(pool, 6)
+        torch.cuda.synchronize()
+        runs[mode] = st
+    a, b = runs["sync"], runs["pipe"]
+    assert int(torch.count_nonzero(a.tables.state)) > 0
+    assert torch.equal(a.tables.weights, b.tables.weights)
+    assert torch.equal(a.tables.state, b.tables.state)
+    assert torch.equal(a.params, b.params) and torch.equal(a.exp_avg_sq, b.exp_avg_sq)
+    assert float(a.loss) == float(b.loss)
+
+
 def test_sharded_overflow_raises(device):
     from two_tower_recommender_model_amd import _lib
     from two_tower_recommender_model_amd.sharded import FusedShardedTwoTowerStep, ThreadComm

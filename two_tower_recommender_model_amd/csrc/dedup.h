@@ -189,6 +189,14 @@ __device__ __forceinline__ void dd_resolve_block(const DedupWs& ws, int rb, int 
 
 size_t dedup_layout(void* base, int64_t L, DedupWs* w);
 
+// host: the one check of a caller's dedup workspace: min_lookups <= max_lookups < 2^18 - 1, the bytes
+// of dedup_layout, 64-B aligned. The dedup exports tell the defects apart (max_lookups out of range
+// and misaligned: TT_EINVAL; null / too small: TT_ECAPACITY). one_code: the launches that take the
+// workspace beside their own arguments (T1's gather, T2, the ring's insert, the owners' gathers)
+// answer TT_ECAPACITY "dedup workspace too small / misaligned" for every defect.
+int check_dedup_ws(const void* workspace, size_t ws_bytes, int64_t max_lookups, int64_t min_lookups, const char* what,
+                   bool one_code);
+
 // arguments of the update launch (dd_adagrad_kernel, or a role of a combined launch)
 struct DdUpdateArgs {
   EmbMeta m;           // tables; features map lookup i = f * B + b to its gradient row
@@ -473,9 +481,7 @@ __device__ __forceinline__ void dd_hot_role(const GradMap& gm, int64_t n,
 }
 
 // host: validate + fill the update launch's arguments; *grid = its workgroup count
-int dedup_update_args(const tt_table_meta_t* tables, int T, const tt_feature_meta_t* features, int F, int64_t B,
-                      const float* grad, int64_t ldg, float* weights, float* state, float lr, float eps,
-                      void* workspace, size_t ws_bytes, int64_t max_lookups, DdUpdateArgs& a, int64_t* grid);
+int dedup_update_args(const tt_adagrad_role_t& g, DdUpdateArgs& a, int64_t* grid);
 
 // the slot part of the update: DD_SPH slots per half-wave (sp, their first 128 B in dw, hq >= 0
 // for a slot to take), gradient rows summed in ascending lookup order, row-wise Adagrad, the slot

@@ -111,41 +111,43 @@ __global__ void __launch_bounds__(256) dd_adagrad_kernel(DdUpdateArgs a) {
   dd_update_block(a, (int)blockIdx.x, smem);
 }
 
-static int check_dd_ws(void* workspace, size_t ws_bytes, int64_t max_lookups, const char* what) {
-  if (max_lookups < 1 || max_lookups >= (int64_t)DD_CNT_MASK)
-    return fail(TT_EINVAL, std::string(what) + ": max_lookups out of range");
-  if (!workspace || ws_bytes < dedup_layout(nullptr, max_lookups, nullptr))
-    return fail(TT_ECAPACITY, std::string(what) + ": workspace too small");
-  if (reinterpret_cast<uintptr_t>(workspace) & 63) return fail(TT_EINVAL, std::string(what) + ": workspace not 64-B aligned");
+int check_dedup_ws(const void* workspace, size_t ws_bytes, int64_t max_lookups, int64_t min_lookups, const char* what,
+                   bool one_code) {
+  const std::string w(what);
+  const bool range = max_lookups < min_lookups || max_lookups >= (int64_t)DD_CNT_MASK;
+  const bool small = !range && (!workspace || ws_bytes < dedup_layout(nullptr, max_lookups, nullptr));
+  const bool misaligned = (reinterpret_cast<uintptr_t>(workspace) & 63) != 0;
+  if (one_code)
+    return range || small || misaligned ? fail(TT_ECAPACITY, w + ": dedup workspace too small / misaligned") : TT_OK;
+  if (range) return fail(TT_EINVAL, w + ": max_lookups out of range");
+  if (small) return fail(TT_ECAPACITY, w + ": workspace too small");
+  if (misaligned) return fail(TT_EINVAL, w + ": workspace not 64-B aligned");
   return TT_OK;
 }
 
-
-int dedup_update_args(const tt_table_meta_t* tables, int T, const tt_feature_meta_t* features, int F, int64_t B,
-                      const float* grad, int64_t ldg, float* weights, float* state, float lr, float eps,
-                      void* workspace, size_t ws_bytes, int64_t max_lookups, DdUpdateArgs& a, int64_t* grid) {
-  int rc = pack_meta(a.m, tables, T, features, F, B);
+int dedup_update_args(const tt_adagrad_role_t& g, DdUpdateArgs& a, int64_t* grid) {
+  int rc = pack_meta(a.m, g.tables, g.T, g.features, g.F, g.B);
   if (rc) return rc;
-  rc = check_dd_ws(workspace, ws_bytes, max_lookups, "dedup_rowwise_adagrad");
+  rc = check_dedup_ws(g.dedup_ws, g.dedup_ws_bytes, g.dedup_max_lookups, 1, "dedup_rowwise_adagrad", false);
   if (rc) return rc;
-  const int64_t n = (int64_t)F * B;
+  const int64_t max_lookups = g.dedup_max_lookups, n = (int64_t)g.F * g.B;
   if (n > max_lookups) return fail(TT_ECAPACITY, "dedup_rowwise_adagrad: F*B > max_lookups");
-  if (!grad || !weights || !state) return fail(TT_EINVAL, "dedup_rowwise_adagrad: null pointer");
-  if ((ldg % 4) || (reinterpret_cast<uintptr_t>(grad) & 15) || (reinterpret_cast<uintptr_t>(weights) & 15))
+  if (!g.grad || !g.weights || !g.state) return fail(TT_EINVAL, "dedup_rowwise_adagrad: null pointer");
+  if ((g.ldg % 4) || (reinterpret_cast<uintptr_t>(g.grad) & 15) || (reinterpret_cast<uintptr_t>(g.weights) & 15))
     return fail(TT_EINVAL, "dedup_rowwise_adagrad: grad/weights must be 16-B aligned with ldg % 4 == 0");
-  for (int t = 0; t < T; ++t)
-    if (tables[t].dim > 128 || tables[t].dim % 4 || tables[t].weight_offset % 4)
+  for (int t = 0; t < g.T; ++t)
+    if (g.tables[t].dim > 128 || g.tables[t].dim % 4 || g.tables[t].weight_offset % 4)
       return fail(TT_EINVAL, "dedup_rowwise_adagrad: needs D % 4 == 0, D <= 128 (16-B rows)");
-  for (int f = 0; f < F; ++f)
-    if (features[f].out_offset % 4) return fail(TT_EINVAL, "dedup_rowwise_adagrad: out_offset % 4 != 0");
-  dedup_layout(workspace, max_lookups, &a.ws);
-  a.grad = grad;
-  a.ldg = ldg;
+  for (int f = 0; f < g.F; ++f)
+    if (g.features[f].out_offset % 4) return fail(TT_EINVAL, "dedup_rowwise_adagrad: out_offset % 4 != 0");
+  dedup_layout(g.dedup_ws, max_lookups, &a.ws);
+  a.grad = g.grad;
+  a.ldg = g.ldg;
   a.n = n;
-  a.weights = weights;
-  a.state = state;
-  a.lr = lr;
-  a.eps = eps;
+  a.weights = g.weights;
+  a.state = g.state;
+  a.lr = g.lr;
+  a.eps = g.eps;
   // a hot row takes a team of up to DD_HOT_TEAM workgroups (dd_hot_role, dd_hot_team)
   // 64 hot workgroups: every one that finds no hot row still checks in, and at uniform ids (no hot
   // rows) 128 cost the ring's tail launch ~0.3 us on MI355X while halving the Zipf tail's hot rows
@@ -170,7 +172,7 @@ size_t tt_dedup_workspace_bytes(int64_t max_lookups) {
 }
 
 int tt_dedup_workspace_init(void* workspace, size_t ws_bytes, int64_t max_lookups, void* stream) {
-  int rc = check_dd_ws(workspace, ws_bytes, max_lookups, "dedup_workspace_init");
+  int rc = check_dedup_ws(workspace, ws_bytes, max_lookups, 1, "dedup_workspace_init", false);
   if (rc) return rc;
   DedupWs w;
   dedup_layout(workspace, max_lookups, &w);
@@ -186,7 +188,7 @@ int tt_dedup_workspace_init(void* workspace, size_t ws_bytes, int64_t max_lookup
 }
 
 int tt_dedup_resolve(void* workspace, size_t ws_bytes, int64_t max_lookups, void* stream) {
-  int rc = check_dd_ws(workspace, ws_bytes, max_lookups, "dedup_resolve");
+  int rc = check_dedup_ws(workspace, ws_bytes, max_lookups, 1, "dedup_resolve", false);
   if (rc) return rc;
   DedupWs w;
   dedup_layout(workspace, max_lookups, &w);
@@ -213,7 +215,7 @@ int tt_dedup_insert_cols(const tt_table_meta_t* tables, int T, const tt_feature_
     ca.num_emb[f] = num_embeddings[f];
   }
   if (max_lookups < (int64_t)F * B) return fail(TT_ECAPACITY, "dedup_insert_cols: max_lookups < F*B");
-  rc = check_dd_ws(workspace, ws_bytes, max_lookups, "dedup_insert_cols");
+  rc = check_dedup_ws(workspace, ws_bytes, max_lookups, 1, "dedup_insert_cols", false);
   if (rc) return rc;
   const int64_t n = (int64_t)F * B;
   if (n == 0) return TT_OK;
@@ -229,7 +231,7 @@ int tt_dedup_insert_segments(const int64_t* keys, const int32_t* counts, int64_t
   if (num_segments < 0 || seg_capacity < 0) return fail(TT_EINVAL, "dedup_insert_segments: negative size");
   const int64_t n = num_segments * seg_capacity;
   if (max_lookups < n) return fail(TT_ECAPACITY, "dedup_insert_segments: max_lookups < segments x capacity");
-  int rc = check_dd_ws(workspace, ws_bytes, max_lookups, "dedup_insert_segments");
+  int rc = check_dedup_ws(workspace, ws_bytes, max_lookups, 1, "dedup_insert_segments", false);
   if (rc) return rc;
   if (n == 0) return TT_OK;
   if (!keys || !counts) return fail(TT_EINVAL, "dedup_insert_segments: null pointer");
@@ -243,10 +245,13 @@ int tt_dedup_insert_segments(const int64_t* keys, const int32_t* counts, int64_t
 int tt_dedup_rowwise_adagrad(const tt_table_meta_t* tables, int T, const tt_feature_meta_t* features, int F,
                              int64_t B, const float* grad, int64_t ldg, float* weights, float* state, float lr,
                              float eps, void* workspace, size_t ws_bytes, int64_t max_lookups, void* stream) {
+  tt_adagrad_role_t g{};
+  g.tables = tables, g.T = T, g.F = F, g.features = features, g.B = B;
+  g.grad = grad, g.ldg = ldg, g.weights = weights, g.state = state, g.lr = lr, g.eps = eps;
+  g.dedup_ws = workspace, g.dedup_ws_bytes = ws_bytes, g.dedup_max_lookups = max_lookups;
   DdUpdateArgs a{};
   int64_t grid = 0;
-  int rc = dedup_update_args(tables, T, features, F, B, grad, ldg, weights, state, lr, eps, workspace, ws_bytes,
-                             max_lookups, a, &grid);
+  int rc = dedup_update_args(g, a, &grid);
   if (rc) return rc;
   dd_adagrad_kernel<<<dim3((unsigned)grid), dim3(256), 0, as_stream(stream)>>>(a);
   return check_launch("dedup_rowwise_adagrad");

@@ -257,9 +257,14 @@ __device__ __forceinline__ void shard_gather_block(const GatherSegArgs& a, int b
     if (a.dd_on && hl == 0 && iu[u] < n) dd_insert_finish(a.dd, pend[u], (int32_t)iu[u]);
 }
 
-int gather_segs_args(const float* weights, const tt_table_meta_t* tables, int T, int F, int W, const int64_t* recv,
-                     int64_t block_i64, int64_t counts_i64, const int64_t* seg_off, int64_t slots, void* rows_out,
-                     int64_t out_stride, int32_t* bad, void* dedup_ws, size_t dedup_ws_bytes,
-                     int64_t dedup_max_lookups, GatherSegArgs& a);
+// host: the route's arguments from its role (tt_shard_route_cols / _segs and the fused launches of
+// csrc/tower.hip). seg_capacity: the uniform layout of tt_shard_route_cols (r.segs and r.pos_out
+// unused), or RT_SEGS: the segment table r.segs. B = 0 passes (the exports then launch nothing).
+constexpr int64_t RT_SEGS = -1;
+int route_args(const tt_route_role_t& r, int64_t B, int64_t seg_capacity, const char* what, RouteArgs& a);
+
+// host: the owner-side gather's arguments from its role (tt_shard_gather_segs_bf16 and launch G of
+// csrc/tower.hip, whose role may carry direct stores); F and W are the route's
+int gather_segs_args(const tt_gather_role_t& ga, int F, int W, GatherSegArgs& a);
 
 }  // namespace tt

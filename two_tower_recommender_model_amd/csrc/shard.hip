@@ -105,53 +105,108 @@ __global__ void __launch_bounds__(256) shard_gather_rows_kernel(GatherArgs a) {
 
 __global__ void __launch_bounds__(256) shard_gather_segs_kernel(GatherSegArgs a) { shard_gather_block(a, (int)blockIdx.x); }
 
-// host: the owner-side gather's arguments (tt_shard_gather_segs_bf16 and the pipelined step's
-// combined launch in csrc/tower.hip)
-int gather_segs_args(const float* weights, const tt_table_meta_t* tables, int T, int F, int W, const int64_t* recv,
-                     int64_t block_i64, int64_t counts_i64, const int64_t* seg_off, int64_t slots, void* rows_out,
-                     int64_t out_stride, int32_t* bad, void* dedup_ws, size_t dedup_ws_bytes,
-                     int64_t dedup_max_lookups, GatherSegArgs& a) {
+// host: the route's checks and arguments, once (shard.h); `what` prefixes the messages
+int route_args(const tt_route_role_t& r, int64_t B, int64_t seg_capacity, const char* what, RouteArgs& a) {
+  const std::string w(what);
+  const int F = r.F, W = r.W;
+  const bool segs = seg_capacity == RT_SEGS;
+  if (F < 1 || F > TT_MAX_FEATURES) return fail(TT_EINVAL, w + ": feature count out of range");
+  if (W < 1 || W > RT_MAXW) return fail(TT_EINVAL, w + ": 1..16 ranks supported");
+  if (B < 0 || (!segs && (seg_capacity < 1 || seg_capacity > INT32_MAX / ((int64_t)W * F))))
+    return fail(TT_EINVAL, w + ": bad batch / segment capacity");
+  if (r.id_dtype != TT_I32 && r.id_dtype != TT_I64) return fail(TT_EINVAL, w + ": ids must be int32/int64");
+  if (!r.cols || !r.num_embeddings || !r.block_sizes || !r.owners || !r.send || !r.pos_in || !r.overflow ||
+      (segs && (!r.segs || !r.pos_out)))
+    return fail(TT_EINVAL, w + ": null pointer");
+  if (!r.route_ws || r.route_ws_bytes < tt_shard_route_workspace_bytes(F, B))
+    return fail(TT_ECAPACITY, w + ": workspace too small");
+  for (int f = 0; f < F; ++f) {
+    const int64_t ne = r.num_embeddings[f], bs = r.block_sizes[f];
+    if (!r.cols[f] || ne < 1) return fail(TT_EINVAL, w + ": bad column");
+    if (bs < 0 || (bs == 0 && (r.owners[f] < 0 || r.owners[f] >= W)))
+      return fail(TT_EINVAL, w + ": bad sharding of a feature");
+    if (bs > 0 && (ne + bs - 1) / bs > W) return fail(TT_EINVAL, w + ": row blocks exceed the rank count");
+    if ((bs > 0 ? bs : ne) >= (1ll << DD_TABLE_SHIFT)) return fail(TT_EINVAL, w + ": local rows >= 2^40");
+    a.col[f] = r.cols[f];
+    a.num_emb[f] = ne;
+    a.block[f] = bs;
+    a.owner[f] = r.owners[f];
+  }
+  a.id_dtype = r.id_dtype;
+  a.F = F;
+  a.W = W;
+  a.B = B;
+  a.C = segs ? 1 : seg_capacity;
+  a.nblk = (int)ceil_div(B, RT_BLOCK);
+  a.send = r.send;
+  a.pos = r.pos_in;
+  a.overflow = r.overflow;
+  if (segs) {
+    a.pos_out = r.pos_out;
+    a.segs = r.segs;
+  }
+  char* ws = reinterpret_cast<char*>(r.route_ws);
+  a.dl = reinterpret_cast<int64_t*>(ws);
+  a.cnt = reinterpret_cast<int32_t*>(ws + align_up(sizeof(int64_t) * (size_t)F * (size_t)B, 256));
+  return TT_OK;
+}
+
+// host: the owner-side gather's checks and arguments (shard.h)
+int gather_segs_args(const tt_gather_role_t& ga, int F, int W, GatherSegArgs& a) {
+  const int T = ga.T;
+  const int64_t slots = ga.slots;
   if (T < 1 || T > TT_MAX_TABLES || F < 1 || F > TT_MAX_FEATURES || F > T || W < 1 || slots < 0 ||
       (int64_t)W * slots >= (1ll << 31))
     return fail(TT_EINVAL, "shard_gather_segs: bad sizes");
-  if (!weights || !tables || !recv || !rows_out || !bad || !seg_off)
+  if (!ga.weights || !ga.tables || !ga.recv || !ga.rows_out || !ga.bad || !ga.seg_off)
     return fail(TT_EINVAL, "shard_gather_segs: null pointer");
   a = GatherSegArgs{};
-  a.D = tables[0].dim;
+  a.D = ga.tables[0].dim;
   for (int t = 0; t < T; ++t) {
-    if (tables[t].dim != a.D) return fail(TT_EINVAL, "shard_gather_segs: tables must share one dim");
-    if (tables[t].weight_offset % 4) return fail(TT_EINVAL, "shard_gather_segs: rows must be 16-B aligned");
-    a.tables[t] = tables[t];
+    if (ga.tables[t].dim != a.D) return fail(TT_EINVAL, "shard_gather_segs: tables must share one dim");
+    if (ga.tables[t].weight_offset % 4) return fail(TT_EINVAL, "shard_gather_segs: rows must be 16-B aligned");
+    a.tables[t] = ga.tables[t];
   }
-  if (a.D % 4 || (reinterpret_cast<uintptr_t>(weights) & 15) || (reinterpret_cast<uintptr_t>(rows_out) & 7))
+  if (a.D % 4 || (reinterpret_cast<uintptr_t>(ga.weights) & 15) || (reinterpret_cast<uintptr_t>(ga.rows_out) & 7))
     return fail(TT_EINVAL, "shard_gather_segs: D % 4 == 0 and aligned buffers required");
   for (int f = 0; f <= F; ++f) {
-    a.seg_off[f] = f < F ? seg_off[f] : slots;
+    a.seg_off[f] = f < F ? ga.seg_off[f] : slots;
     if (a.seg_off[f] < 0 || a.seg_off[f] > slots || (f && a.seg_off[f] < a.seg_off[f - 1]))
       return fail(TT_EINVAL, "shard_gather_segs: segment offsets must ascend within [0, slots]");
   }
-  if (block_i64 < counts_i64 + F + slots || counts_i64 < 0) return fail(TT_EINVAL, "shard_gather_segs: bad block layout");
+  if (ga.block_i64 < ga.counts_i64 + F + slots || ga.counts_i64 < 0)
+    return fail(TT_EINVAL, "shard_gather_segs: bad block layout");
   const int64_t n = (int64_t)W * slots;
   if (n > INT32_MAX) return fail(TT_EINVAL, "shard_gather_segs: too many slots");
-  a.weights = weights;
+  a.weights = ga.weights;
   a.T = T;
   a.F = F;
   a.W = W;
   a.S = slots;
-  if (out_stride < slots) return fail(TT_EINVAL, "shard_gather_segs: out_stride < slots");
-  a.out_stride = out_stride;
-  a.blk64 = block_i64;
-  a.cnt64 = counts_i64;
-  a.recv = recv;
-  a.rows_out = reinterpret_cast<__bf16*>(rows_out);
-  a.bad = bad;
-  if (dedup_ws) {
-    if (dedup_max_lookups < n || dedup_max_lookups >= (int64_t)DD_CNT_MASK ||
-        dedup_ws_bytes < dedup_layout(nullptr, dedup_max_lookups, nullptr) ||
-        (reinterpret_cast<uintptr_t>(dedup_ws) & 63))
-      return fail(TT_ECAPACITY, "shard_gather_segs: dedup workspace too small / misaligned");
-    dedup_layout(dedup_ws, dedup_max_lookups, &a.dd);
+  if (ga.out_stride < slots) return fail(TT_EINVAL, "shard_gather_segs: out_stride < slots");
+  a.out_stride = ga.out_stride;
+  a.blk64 = ga.block_i64;
+  a.cnt64 = ga.counts_i64;
+  a.recv = ga.recv;
+  a.rows_out = reinterpret_cast<__bf16*>(ga.rows_out);
+  a.bad = ga.bad;
+  if (ga.dedup_ws) {
+    if (int rc = check_dedup_ws(ga.dedup_ws, ga.dedup_ws_bytes, ga.dedup_max_lookups, n, "shard_gather_segs", true))
+      return rc;
+    dedup_layout(ga.dedup_ws, ga.dedup_max_lookups, &a.dd);
     a.dd_on = 1;
+  }
+  if (ga.direct) {  // launch G: source s's rows go straight to its mapped receive buffer
+    const tt_peer_direct_t& x = *ga.direct;
+    if (int rc = peer_direct_check(x, "tower_grads_place_gather")) return rc;
+    if (x.W != W) return fail(TT_EINVAL, "tower_grads_place_gather: direct.W must be the route's W");
+    for (int s = 0; s < W; ++s) {
+      if (x.first_row[s] != (int64_t)s * ga.out_stride)
+        return fail(TT_EINVAL, "tower_grads_place_gather: direct.first_row[s] must be s * out_stride");
+      a.dblk[s] = reinterpret_cast<__bf16*>(x.row0[s]);
+    }
+    a.dW = W;
+    a.epoch = x.epoch;
   }
   return TT_OK;
 }
@@ -239,80 +294,51 @@ int tt_shard_route_cols(int F, int64_t B, const void* const* cols, int id_dtype,
                         const int64_t* block_sizes, const int32_t* owners, int W, int64_t seg_capacity,
                         int64_t* send, int32_t* pos, int32_t* overflow, void* workspace, size_t ws_bytes,
                         void* stream) {
-  if (F < 1 || F > TT_MAX_FEATURES) return fail(TT_EINVAL, "shard_route: feature count out of range");
-  if (W < 1 || W > RT_MAXW) return fail(TT_EINVAL, "shard_route: 1..16 ranks supported");
-  if (B < 0 || seg_capacity < 1 || seg_capacity > INT32_MAX / ((int64_t)W * F))
-    return fail(TT_EINVAL, "shard_route: bad batch / segment capacity");
-  if (id_dtype != TT_I32 && id_dtype != TT_I64) return fail(TT_EINVAL, "shard_route: ids must be int32/int64");
-  if (!cols || !num_embeddings || !block_sizes || !owners || !send || !pos || !overflow)
-    return fail(TT_EINVAL, "shard_route: null pointer");
-  if (!workspace || ws_bytes < tt_shard_route_workspace_bytes(F, B))
-    return fail(TT_ECAPACITY, "shard_route: workspace too small");
+  tt_route_role_t r{};
+  r.F = F, r.id_dtype = id_dtype, r.cols = cols, r.num_embeddings = num_embeddings, r.block_sizes = block_sizes;
+  r.owners = owners, r.W = W, r.send = send, r.pos_in = pos, r.overflow = overflow;
+  r.route_ws = workspace, r.route_ws_bytes = ws_bytes;
   RouteArgs a{};
-  for (int f = 0; f < F; ++f) {
-    if (!cols[f] || num_embeddings[f] < 1) return fail(TT_EINVAL, "shard_route: bad column");
-    if (block_sizes[f] < 0 || (block_sizes[f] == 0 && (owners[f] < 0 || owners[f] >= W)))
-      return fail(TT_EINVAL, "shard_route: bad sharding of a feature");
-    if (block_sizes[f] > 0 && (num_embeddings[f] + block_sizes[f] - 1) / block_sizes[f] > W)
-      return fail(TT_EINVAL, "shard_route: row blocks exceed the rank count");
-    if ((block_sizes[f] > 0 ? block_sizes[f] : num_embeddings[f]) >= (1ll << DD_TABLE_SHIFT))
-      return fail(TT_EINVAL, "shard_route: local rows >= 2^40");
-    a.col[f] = cols[f];
-    a.num_emb[f] = num_embeddings[f];
-    a.block[f] = block_sizes[f];
-    a.owner[f] = owners[f];
-  }
+  if (int rc = route_args(r, B, seg_capacity, "shard_route", a)) return rc;
   if (B == 0) return TT_OK;
-  a.id_dtype = id_dtype;
-  a.F = F;
-  a.W = W;
-  a.B = B;
-  a.C = seg_capacity;
-  a.nblk = (int)ceil_div(B, RT_BLOCK);
-  a.send = send;
-  a.pos = pos;
-  a.overflow = overflow;
-  char* ws = reinterpret_cast<char*>(workspace);
-  a.dl = reinterpret_cast<int64_t*>(ws);
-  a.cnt = reinterpret_cast<int32_t*>(ws + align_up(sizeof(int64_t) * (size_t)F * (size_t)B, 256));
   const dim3 grid(a.nblk, F);
   shard_route_count_kernel<<<grid, dim3(RT_BLOCK), 0, as_stream(stream)>>>(a);
   shard_route_place_kernel<false><<<grid, dim3(RT_BLOCK), 0, as_stream(stream)>>>(a);
   return check_launch("shard_route");
 }
 
-static int gather_rows(const float* weights, const tt_table_meta_t* tables, int T, int F, int W,
-                       int64_t seg_capacity, const int64_t* recv, float* rows_out, int32_t* bad, void* dedup_ws,
-                       size_t dedup_ws_bytes, int64_t dedup_max_lookups, void* stream, int out_bf16) {
+// the uniform-capacity gather of the owner's role (its weights, tables, T, recv, rows_out, bad and
+// dedup fields; rows_out fp32, or bf16 when out_bf16)
+static int gather_rows(const tt_gather_role_t& ga, int F, int W, int64_t seg_capacity, int out_bf16, void* stream) {
+  const int T = ga.T;
   if (T < 1 || T > TT_MAX_TABLES || F < 1 || F > TT_MAX_FEATURES || W < 1 || seg_capacity < 1)
     return fail(TT_EINVAL, "shard_gather_rows: bad sizes");
-  if (!weights || !tables || !recv || !rows_out || !bad) return fail(TT_EINVAL, "shard_gather_rows: null pointer");
+  if (!ga.weights || !ga.tables || !ga.recv || !ga.rows_out || !ga.bad)
+    return fail(TT_EINVAL, "shard_gather_rows: null pointer");
   GatherArgs a{};
-  a.D = tables[0].dim;
+  a.D = ga.tables[0].dim;
   for (int t = 0; t < T; ++t) {
-    if (tables[t].dim != a.D) return fail(TT_EINVAL, "shard_gather_rows: tables must share one dim");
-    if (tables[t].weight_offset % 4) return fail(TT_EINVAL, "shard_gather_rows: rows must be 16-B aligned");
-    a.tables[t] = tables[t];
+    if (ga.tables[t].dim != a.D) return fail(TT_EINVAL, "shard_gather_rows: tables must share one dim");
+    if (ga.tables[t].weight_offset % 4) return fail(TT_EINVAL, "shard_gather_rows: rows must be 16-B aligned");
+    a.tables[t] = ga.tables[t];
   }
-  if (a.D % 4 || (reinterpret_cast<uintptr_t>(weights) & 15) || (reinterpret_cast<uintptr_t>(rows_out) & 15))
+  if (a.D % 4 || (reinterpret_cast<uintptr_t>(ga.weights) & 15) || (reinterpret_cast<uintptr_t>(ga.rows_out) & 15))
     return fail(TT_EINVAL, "shard_gather_rows: D % 4 == 0 and 16-B aligned buffers required");
   const int64_t n = (int64_t)W * F * seg_capacity;
   if (n > INT32_MAX) return fail(TT_EINVAL, "shard_gather_rows: too many slots");
-  a.weights = weights;
+  a.weights = ga.weights;
   a.T = T;
   a.F = F;
   a.W = W;
   a.C = seg_capacity;
-  a.recv = recv;
-  a.rows_out = rows_out;
+  a.recv = ga.recv;
+  a.rows_out = reinterpret_cast<float*>(ga.rows_out);
   a.out_bf16 = out_bf16;
-  a.bad = bad;
-  if (dedup_ws) {
-    if (dedup_max_lookups < n || dedup_max_lookups >= (int64_t)DD_CNT_MASK ||
-        dedup_ws_bytes < dedup_layout(nullptr, dedup_max_lookups, nullptr) ||
-        (reinterpret_cast<uintptr_t>(dedup_ws) & 63))
-      return fail(TT_ECAPACITY, "shard_gather_rows: dedup workspace too small / misaligned");
-    dedup_layout(dedup_ws, dedup_max_lookups, &a.dd);
+  a.bad = ga.bad;
+  if (ga.dedup_ws) {
+    if (int rc = check_dedup_ws(ga.dedup_ws, ga.dedup_ws_bytes, ga.dedup_max_lookups, n, "shard_gather_rows", true))
+      return rc;
+    dedup_layout(ga.dedup_ws, ga.dedup_max_lookups, &a.dd);
     a.dd_on = 1;
   }
   const int64_t grid = ceil_div(n, 8);
@@ -320,61 +346,41 @@ static int gather_rows(const float* weights, const tt_table_meta_t* tables, int 
   return check_launch("shard_gather_rows");
 }
 
+// the gather role of the two owner-side exports' shared arguments
+static tt_gather_role_t gather_role(const float* weights, const tt_table_meta_t* tables, int T, const int64_t* recv,
+                                    void* rows_out, int32_t* bad, void* dedup_ws, size_t dedup_ws_bytes,
+                                    int64_t dedup_max_lookups) {
+  tt_gather_role_t ga{};
+  ga.weights = weights, ga.tables = tables, ga.T = T, ga.recv = recv, ga.rows_out = rows_out, ga.bad = bad;
+  ga.dedup_ws = dedup_ws, ga.dedup_ws_bytes = dedup_ws_bytes, ga.dedup_max_lookups = dedup_max_lookups;
+  return ga;
+}
+
 int tt_shard_gather_rows(const float* weights, const tt_table_meta_t* tables, int T, int F, int W,
                          int64_t seg_capacity, const int64_t* recv, float* rows_out, int32_t* bad, void* dedup_ws,
                          size_t dedup_ws_bytes, int64_t dedup_max_lookups, void* stream) {
-  return gather_rows(weights, tables, T, F, W, seg_capacity, recv, rows_out, bad, dedup_ws, dedup_ws_bytes,
-                     dedup_max_lookups, stream, 0);
+  return gather_rows(gather_role(weights, tables, T, recv, rows_out, bad, dedup_ws, dedup_ws_bytes, dedup_max_lookups),
+                     F, W, seg_capacity, 0, stream);
 }
 
 int tt_shard_gather_rows_bf16(const float* weights, const tt_table_meta_t* tables, int T, int F, int W,
                               int64_t seg_capacity, const int64_t* recv, void* rows_out, int32_t* bad, void* dedup_ws,
                               size_t dedup_ws_bytes, int64_t dedup_max_lookups, void* stream) {
-  return gather_rows(weights, tables, T, F, W, seg_capacity, recv, reinterpret_cast<float*>(rows_out), bad, dedup_ws,
-                     dedup_ws_bytes, dedup_max_lookups, stream, 1);
+  return gather_rows(gather_role(weights, tables, T, recv, rows_out, bad, dedup_ws, dedup_ws_bytes, dedup_max_lookups),
+                     F, W, seg_capacity, 1, stream);
 }
 
 int tt_shard_route_segs(int F, int64_t B, const void* const* cols, int id_dtype, const int64_t* num_embeddings,
                         const int64_t* block_sizes, const int32_t* owners, int W, const tt_shard_seg_t* segs,
                         int64_t* send, int32_t* pos_in, int32_t* pos_out, int32_t* overflow, void* workspace,
                         size_t ws_bytes, void* stream) {
-  if (F < 1 || F > TT_MAX_FEATURES) return fail(TT_EINVAL, "shard_route_segs: feature count out of range");
-  if (W < 1 || W > RT_MAXW) return fail(TT_EINVAL, "shard_route_segs: 1..16 ranks supported");
-  if (B < 0) return fail(TT_EINVAL, "shard_route_segs: negative batch");
-  if (id_dtype != TT_I32 && id_dtype != TT_I64) return fail(TT_EINVAL, "shard_route_segs: ids must be int32/int64");
-  if (!cols || !num_embeddings || !block_sizes || !owners || !segs || !send || !pos_in || !pos_out || !overflow)
-    return fail(TT_EINVAL, "shard_route_segs: null pointer");
-  if (!workspace || ws_bytes < tt_shard_route_workspace_bytes(F, B))
-    return fail(TT_ECAPACITY, "shard_route_segs: workspace too small");
+  tt_route_role_t r{};
+  r.F = F, r.id_dtype = id_dtype, r.cols = cols, r.num_embeddings = num_embeddings, r.block_sizes = block_sizes;
+  r.owners = owners, r.W = W, r.segs = segs, r.send = send, r.pos_in = pos_in, r.pos_out = pos_out;
+  r.overflow = overflow, r.route_ws = workspace, r.route_ws_bytes = ws_bytes;
   RouteArgs a{};
-  for (int f = 0; f < F; ++f) {
-    if (!cols[f] || num_embeddings[f] < 1) return fail(TT_EINVAL, "shard_route_segs: bad column");
-    if (block_sizes[f] < 0 || (block_sizes[f] == 0 && (owners[f] < 0 || owners[f] >= W)))
-      return fail(TT_EINVAL, "shard_route_segs: bad sharding of a feature");
-    if (block_sizes[f] > 0 && (num_embeddings[f] + block_sizes[f] - 1) / block_sizes[f] > W)
-      return fail(TT_EINVAL, "shard_route_segs: row blocks exceed the rank count");
-    if ((block_sizes[f] > 0 ? block_sizes[f] : num_embeddings[f]) >= (1ll << DD_TABLE_SHIFT))
-      return fail(TT_EINVAL, "shard_route_segs: local rows >= 2^40");
-    a.col[f] = cols[f];
-    a.num_emb[f] = num_embeddings[f];
-    a.block[f] = block_sizes[f];
-    a.owner[f] = owners[f];
-  }
+  if (int rc = route_args(r, B, RT_SEGS, "shard_route_segs", a)) return rc;
   if (B == 0) return TT_OK;
-  a.id_dtype = id_dtype;
-  a.F = F;
-  a.W = W;
-  a.B = B;
-  a.C = 1;
-  a.nblk = (int)ceil_div(B, RT_BLOCK);
-  a.send = send;
-  a.pos = pos_in;
-  a.pos_out = pos_out;
-  a.segs = segs;
-  a.overflow = overflow;
-  char* ws = reinterpret_cast<char*>(workspace);
-  a.dl = reinterpret_cast<int64_t*>(ws);
-  a.cnt = reinterpret_cast<int32_t*>(ws + align_up(sizeof(int64_t) * (size_t)F * (size_t)B, 256));
   const dim3 grid(a.nblk, F);
   shard_route_count_kernel<<<grid, dim3(RT_BLOCK), 0, as_stream(stream)>>>(a);
   shard_route_place_kernel<true><<<grid, dim3(RT_BLOCK), 0, as_stream(stream)>>>(a);
@@ -385,10 +391,10 @@ int tt_shard_gather_segs_bf16(const float* weights, const tt_table_meta_t* table
                               const int64_t* recv, int64_t block_i64, int64_t counts_i64, const int64_t* seg_off,
                               int64_t slots, void* rows_out, int64_t out_stride, int32_t* bad, void* dedup_ws,
                               size_t dedup_ws_bytes, int64_t dedup_max_lookups, void* stream) {
+  tt_gather_role_t ga = gather_role(weights, tables, T, recv, rows_out, bad, dedup_ws, dedup_ws_bytes, dedup_max_lookups);
+  ga.block_i64 = block_i64, ga.counts_i64 = counts_i64, ga.seg_off = seg_off, ga.slots = slots, ga.out_stride = out_stride;
   GatherSegArgs a{};
-  int rc = gather_segs_args(weights, tables, T, F, W, recv, block_i64, counts_i64, seg_off, slots, rows_out, out_stride,
-                            bad, dedup_ws, dedup_ws_bytes, dedup_max_lookups, a);
-  if (rc) return rc;
+  if (int rc = gather_segs_args(ga, F, W, a)) return rc;
   const int64_t n = (int64_t)W * slots;
   if (n == 0) return TT_OK;
   shard_gather_segs_kernel<<<dim3((unsigned)ceil_div(ceil_div(n, GS_SL), 8)), dim3(256), 0, as_stream(stream)>>>(a);

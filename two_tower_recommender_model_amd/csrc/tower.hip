@@ -2899,6 +2899,15 @@ static int tower_layout(const tt_tower_shape_t* s, int64_t B, TowerLayout* lay) 
   return TT_OK;
 }
 
+// the layout of a caller's workspace: the shape checks, then the workspace's size
+static int tower_ws_layout(const tt_tower_shape_t* s, int64_t B, const void* workspace, size_t ws_bytes,
+                           TowerLayout* lay) {
+  int rc = tower_layout(s, B, lay);
+  if (rc) return rc;
+  if (!workspace || ws_bytes < lay->total) return fail(TT_ECAPACITY, "tower: workspace too small");
+  return TT_OK;
+}
+
 }  // namespace tt
 
 using namespace tt;
@@ -2920,9 +2929,8 @@ size_t tt_tower_workspace_bytes(const tt_tower_shape_t* shape, int64_t B) {
 int tt_tower_workspace_init(const tt_tower_shape_t* shape, int64_t B, void* workspace, size_t ws_bytes,
                             void* stream) {
   TowerLayout L;
-  int rc = tower_layout(shape, B, &L);
+  int rc = tower_ws_layout(shape, B, workspace, ws_bytes, &L);
   if (rc) return rc;
-  if (!workspace || ws_bytes < L.total) return fail(TT_ECAPACITY, "tower: workspace too small");
   hipStream_t st = as_stream(stream);
   char* ws = reinterpret_cast<char*>(workspace);
   if (hipMemsetAsync(ws, 0, L.total, st) != hipSuccess) return fail(TT_EINVAL, "tower: memset failed");
@@ -2942,36 +2950,59 @@ int tt_tower_workspace_init(const tt_tower_shape_t* shape, int64_t B, void* work
 }  // extern "C"
 
 namespace tt {
-// the NEXT batch's insert role (tt_tower_wgrad_pre_insert, tt_tower_tail_rowwise_adagrad_insert)
-static int insert_args(int64_t B, const void* const* next_cols, int id_dtype, const int64_t* num_embeddings,
-                       const int32_t* dedup_tables, void* next_dedup_ws, int64_t dedup_max_lookups, InsertArgs& ins) {
+// the NEXT batch's insert role (WGRAD | INSERT, and the ring tail WGRAD | INSERT | ADAGRAD): its checks
+// and arguments; the dedup workspace holds both towers' B lookups
+static int insert_args(const tt_insert_role_t& in, int64_t B, const char* what, InsertArgs& ins) {
+  const std::string w(what);
+  if (!in.next_cols || !in.num_embeddings || !in.dedup_tables || !in.next_dedup_ws)
+    return fail(TT_EINVAL, w + ": null pointer");
+  if (in.id_dtype != TT_I32 && in.id_dtype != TT_I64) return fail(TT_EINVAL, w + ": ids must be int32/int64");
+  if (int rc = check_dedup_ws(in.next_dedup_ws, in.dedup_ws_bytes, in.dedup_max_lookups, 2 * B, what, true)) return rc;
   for (int t = 0; t < 2; ++t) {
-    if (!next_cols[t] || num_embeddings[t] < 1 || num_embeddings[t] >= (1ll << DD_TABLE_SHIFT) ||
-        dedup_tables[t] < 0 || dedup_tables[t] >= TT_MAX_TABLES)
+    if (!in.next_cols[t] || in.num_embeddings[t] < 1 || in.num_embeddings[t] >= (1ll << DD_TABLE_SHIFT) ||
+        in.dedup_tables[t] < 0 || in.dedup_tables[t] >= TT_MAX_TABLES)
       return fail(TT_EINVAL, "tower insert: bad column / table");
-    ins.col[t] = next_cols[t];
-    ins.mod[t] = num_embeddings[t];
-    ins.tab[t] = dedup_tables[t];
+    ins.col[t] = in.next_cols[t];
+    ins.mod[t] = in.num_embeddings[t];
+    ins.tab[t] = in.dedup_tables[t];
   }
-  ins.id_dtype = id_dtype;
+  ins.id_dtype = in.id_dtype;
   ins.B = B;
   // tile-class filing (ins_lookup): 2B / 256 workgroups, B / 2048 of them per (class, tower)
   ins.xcd_wpt = (INS_PT == 1 && B % 2048 == 0) ? (int)(B / 2048) : 0;
-  dedup_layout(next_dedup_ws, dedup_max_lookups, &ins.dd);
+  dedup_layout(in.next_dedup_ws, in.dedup_max_lookups, &ins.dd);
   return TT_OK;
 }
 
 }  // namespace tt
 
 namespace tt {
-// shared by tt_tower_fwd_bwd / tt_tower_fwd_bwd_gather: checks, T1 arguments, launch
+// what every T1 export hands on as it got it: the towers' parameters, the labels, the outputs
+struct T1Common {
+  const float* params;
+  const void* labels;
+  int label_dtype;
+  float grad_scale;
+  float* logits;
+  void* workspace;
+  size_t ws_bytes;
+  void* stream;
+};
+
+// shared by every T1 export: checks, T1 arguments, launch
 static int launch_t1(const tt_tower_shape_t* shape, int64_t B, TowerArgs& a, const float* pooled, int64_t ldp,
-                     float* gpooled, const float* params, const void* labels, int label_dtype, float grad_scale,
-                     float* logits, void* workspace, size_t ws_bytes, void* stream) {
+                     float* gpooled, const T1Common& c) {
+  const float* params = c.params;
+  const void* labels = c.labels;
+  const int label_dtype = c.label_dtype;
+  const float grad_scale = c.grad_scale;
+  float* logits = c.logits;
+  void* workspace = c.workspace;
+  const size_t ws_bytes = c.ws_bytes;
+  void* stream = c.stream;
   TowerLayout L;
-  int rc = tower_layout(shape, B, &L);
+  int rc = tower_ws_layout(shape, B, workspace, ws_bytes, &L);
   if (rc) return rc;
-  if (!workspace || ws_bytes < L.total) return fail(TT_ECAPACITY, "tower: workspace too small");
   if ((!pooled && !a.gcol[0] && !a.gpos[0] && !a.mval && !a.ipos) || (!gpooled && !a.gpos[0] && !a.ipos) || !params ||
       !labels || !logits)
     return fail(TT_EINVAL, "tower: null pointer");
@@ -3093,13 +3124,12 @@ static int launch_t1(const tt_tower_shape_t* shape, int64_t B, TowerArgs& a, con
   return check_launch("tower_fwd_bwd");
 }
 
-// T2 arguments from the shape + workspace (shared by tt_tower_wgrad and the combined launch)
-static int wgrad_args(const tt_tower_shape_t* shape, int64_t B, float* loss, void* workspace, size_t ws_bytes,
-                      WgradArgs& a, int64_t* wgs) {
-  TowerLayout L;
-  int rc = tower_layout(shape, B, &L);
+// T2 arguments from the shape + workspace + WGRAD role (shared by every launch that runs T2); hands
+// back the layout it computed and *wgs = T2's workgroup count
+static int wgrad_args(const tt_tower_shape_t* shape, int64_t B, void* workspace, size_t ws_bytes,
+                      const tt_wgrad_role_t& w, WgradArgs& a, int64_t* wgs, TowerLayout& L) {
+  int rc = tower_ws_layout(shape, B, workspace, ws_bytes, &L);
   if (rc) return rc;
-  if (!workspace || ws_bytes < L.total) return fail(TT_ECAPACITY, "tower: workspace too small");
   char* ws = reinterpret_cast<char*>(workspace);
   a.xt = reinterpret_cast<const __bf16*>(ws + L.o_xt);
   a.act = reinterpret_cast<const __bf16*>(ws + L.o_act);
@@ -3127,7 +3157,7 @@ static int wgrad_args(const tt_tower_shape_t* shape, int64_t B, float* loss, voi
   a.dbpart = reinterpret_cast<const float*>(ws + L.o_dbpart);
   a.nwg = L.nwg;
   a.loss_part = reinterpret_cast<const float*>(ws + L.o_losspart);
-  a.loss = loss;
+  a.loss = w.loss;
   a.nbias = nbias;
   a.tiles_off = (int64_t)L.o_tiles;
 #if TT_EXPERIMENTS
@@ -3138,8 +3168,20 @@ static int wgrad_args(const tt_tower_shape_t* shape, int64_t B, float* loss, voi
   for (int i = 0; i < 16; ++i) {
     a.t2_code[i] = L.t2_code[i];
   }
-  *wgs =(int64_t)L.ntiles * L.S + ceil_div(nbias + 1, 4);
+  if (w.adam_step_state) {  // the loss wave advances Adam's step and writes its scalars for T3
+    a.step_state = w.adam_step_state;
+    a.adam_pre = reinterpret_cast<float*>(ws + L.o_counter);
+    a.lr = w.adam_lr;
+    a.beta1 = w.adam_beta1;
+    a.beta2 = w.adam_beta2;
+  }
+  *wgs = (int64_t)L.ntiles * L.S + ceil_div(nbias + 1, 4);
   return TT_OK;
+}
+
+// the tile list of the register-path T2 in the workspace (tt_tower_workspace_init uploaded it)
+static const WgradTile* wgrad_tiles(void* workspace, const WgradArgs& a) {
+  return reinterpret_cast<const WgradTile*>(reinterpret_cast<char*>(workspace) + a.tiles_off);
 }
 }  // namespace tt
 
@@ -3149,8 +3191,8 @@ int tt_tower_fwd_bwd(const tt_tower_shape_t* shape, int64_t B, const float* pool
                      const float* params, const void* labels, int label_dtype, float grad_scale, float* logits,
                      void* workspace, size_t ws_bytes, void* stream) {
   TowerArgs a{};
-  return launch_t1(shape, B, a, pooled, ldp, gpooled, params, labels, label_dtype, grad_scale, logits, workspace,
-                   ws_bytes, stream);
+  return launch_t1(shape, B, a, pooled, ldp, gpooled,
+                   {params, labels, label_dtype, grad_scale, logits, workspace, ws_bytes, stream});
 }
 
 int tt_tower_fwd_bwd_gather(const tt_tower_shape_t* shape, int64_t B, const void* const* cols, int id_dtype,
@@ -3173,10 +3215,7 @@ int tt_tower_fwd_bwd_gather(const tt_tower_shape_t* shape, int64_t B, const void
   a.pooled_out = pooled_out;
   if (dedup_ws) {
     if (!dedup_tables) return fail(TT_EINVAL, "tower_gather: dedup needs the key table of each tower");
-    if (dedup_max_lookups < 2 * B || dedup_max_lookups >= (int64_t)DD_CNT_MASK ||
-        dedup_ws_bytes < dedup_layout(nullptr, dedup_max_lookups, nullptr) ||
-        (reinterpret_cast<uintptr_t>(dedup_ws) & 63))
-      return fail(TT_ECAPACITY, "tower_gather: dedup workspace too small / misaligned");
+    if (int rc = check_dedup_ws(dedup_ws, dedup_ws_bytes, dedup_max_lookups, 2 * B, "tower_gather", true)) return rc;
     for (int t = 0; t < 2; ++t) {
       if (dedup_tables[t] < 0 || dedup_tables[t] >= TT_MAX_TABLES || num_embeddings[t] >= (1ll << DD_TABLE_SHIFT))
         return fail(TT_EINVAL, "tower_gather: bad dedup table");
@@ -3185,8 +3224,8 @@ int tt_tower_fwd_bwd_gather(const tt_tower_shape_t* shape, int64_t B, const void
     dedup_layout(dedup_ws, dedup_max_lookups, &a.dd);
     a.dd_on = 1;
   }
-  return launch_t1(shape, B, a, nullptr, ldp, gpooled, params, labels, label_dtype, grad_scale, logits, workspace,
-                   ws_bytes, stream);
+  return launch_t1(shape, B, a, nullptr, ldp, gpooled,
+                   {params, labels, label_dtype, grad_scale, logits, workspace, ws_bytes, stream});
 }
 
 int tt_tower_fwd_bwd_kjt(const tt_tower_shape_t* shape, int64_t B, const void* values, int id_dtype,
@@ -3208,14 +3247,12 @@ int tt_tower_fwd_bwd_kjt(const tt_tower_shape_t* shape, int64_t B, const void* v
   a.mval = values;
   a.gid_dtype = id_dtype;
   a.pooled_out = pooled_out;
-  return launch_t1(shape, B, a, nullptr, ldp, gpooled, params, labels, label_dtype, grad_scale, logits, workspace,
-                   ws_bytes, stream);
+  return launch_t1(shape, B, a, nullptr, ldp, gpooled,
+                   {params, labels, label_dtype, grad_scale, logits, workspace, ws_bytes, stream});
 }
 
 static int tower_indexed(const tt_tower_shape_t* shape, int64_t B, const int32_t* const* pos,
-                         const float* const* rows_in, float* const* grad_rows_out, const float* params,
-                         const void* labels, int label_dtype, float grad_scale, float* logits, void* workspace,
-                         size_t ws_bytes, void* stream, int bf16_rows) {
+                         const float* const* rows_in, float* const* grad_rows_out, const T1Common& c, int bf16_rows) {
   if (!pos || !rows_in || !grad_rows_out) return fail(TT_EINVAL, "tower_indexed: null pointer");
   TowerArgs a{};
   a.gsrc_bf16 = bf16_rows;
@@ -3228,34 +3265,35 @@ static int tower_indexed(const tt_tower_shape_t* shape, int64_t B, const int32_t
     a.gdst[t] = grad_rows_out[t];
   }
   return launch_t1(shape, B, a, nullptr,
-                   std::max(shape->in_col[0] + shape->in_dim[0], shape->in_col[1] + shape->in_dim[1]), nullptr, params, labels, label_dtype,
-                   grad_scale, logits, workspace, ws_bytes, stream);
+                   std::max(shape->in_col[0] + shape->in_dim[0], shape->in_col[1] + shape->in_dim[1]), nullptr, c);
 }
 
 int tt_tower_fwd_bwd_indexed(const tt_tower_shape_t* shape, int64_t B, const int32_t* const* pos,
                              const float* const* rows_in, float* const* grad_rows_out, const float* params,
                              const void* labels, int label_dtype, float grad_scale, float* logits, void* workspace,
                              size_t ws_bytes, void* stream) {
-  return tower_indexed(shape, B, pos, rows_in, grad_rows_out, params, labels, label_dtype, grad_scale, logits,
-                       workspace, ws_bytes, stream, 0);
+  return tower_indexed(shape, B, pos, rows_in, grad_rows_out,
+                       {params, labels, label_dtype, grad_scale, logits, workspace, ws_bytes, stream}, 0);
 }
 
 int tt_tower_fwd_bwd_indexed_bf16(const tt_tower_shape_t* shape, int64_t B, const int32_t* const* pos,
                                   const void* const* rows_in, float* const* grad_rows_out, const float* params,
                                   const void* labels, int label_dtype, float grad_scale, float* logits,
                                   void* workspace, size_t ws_bytes, void* stream) {
-  return tower_indexed(shape, B, pos, reinterpret_cast<const float* const*>(rows_in), grad_rows_out, params, labels,
-                       label_dtype, grad_scale, logits, workspace, ws_bytes, stream, 1);
+  return tower_indexed(shape, B, pos, reinterpret_cast<const float* const*>(rows_in), grad_rows_out,
+                       {params, labels, label_dtype, grad_scale, logits, workspace, ws_bytes, stream}, 1);
 }
 
 int tt_tower_wgrad(const tt_tower_shape_t* shape, int64_t B, float* loss, void* workspace, size_t ws_bytes,
                    void* stream) {
+  tt_wgrad_role_t w{};
+  w.loss = loss;
   WgradArgs a{};
   int64_t wgs = 0;
-  int rc = wgrad_args(shape, B, loss, workspace, ws_bytes, a, &wgs);
+  TowerLayout L;
+  int rc = wgrad_args(shape, B, workspace, ws_bytes, w, a, &wgs, L);
   if (rc) return rc;
-  tower_wgrad_kernel<<<dim3((unsigned)wgs), dim3(256), 0, as_stream(stream)>>>(
-      a, reinterpret_cast<const WgradTile*>(reinterpret_cast<char*>(workspace) + a.tiles_off));
+  tower_wgrad_kernel<<<dim3((unsigned)wgs), dim3(256), 0, as_stream(stream)>>>(a, wgrad_tiles(workspace, a));
   return check_launch("tower_wgrad");
 }
 
@@ -3263,79 +3301,71 @@ int tt_tower_wgrad_pre(const tt_tower_shape_t* shape, int64_t B, float* loss, vo
                        int64_t* adam_step_state, float adam_lr, float adam_beta1, float adam_beta2, void* dedup_ws,
                        size_t dedup_ws_bytes, int64_t dedup_max_lookups, void* stream) {
   if (!adam_step_state) return fail(TT_EINVAL, "tower_wgrad_pre: null Adam step state");
+  const tt_wgrad_role_t w{loss, adam_step_state, adam_lr, adam_beta1, adam_beta2};
   WgradArgs a{};
   int64_t wgs = 0;
-  int rc = wgrad_args(shape, B, loss, workspace, ws_bytes, a, &wgs);
+  TowerLayout L;
+  int rc = wgrad_args(shape, B, workspace, ws_bytes, w, a, &wgs, L);
   if (rc) return rc;
   if (dedup_ws) {
-    if (dedup_max_lookups < 1 || dedup_max_lookups >= (int64_t)DD_CNT_MASK ||
-        dedup_ws_bytes < dedup_layout(nullptr, dedup_max_lookups, nullptr) ||
-        (reinterpret_cast<uintptr_t>(dedup_ws) & 63))
-      return fail(TT_ECAPACITY, "tower_wgrad_pre: dedup workspace too small / misaligned");
+    if ((rc = check_dedup_ws(dedup_ws, dedup_ws_bytes, dedup_max_lookups, 1, "tower_wgrad_pre", true))) return rc;
     dedup_layout(dedup_ws, dedup_max_lookups, &a.dd);
     a.n_res = 64;
     wgs += a.n_res;
   }
-  TowerLayout L;
-  tower_layout(shape, B, &L);
-  a.step_state = adam_step_state;
-  a.adam_pre = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + L.o_counter);
-  a.lr = adam_lr;
-  a.beta1 = adam_beta1;
-  a.beta2 = adam_beta2;
-  tower_wgrad_kernel<<<dim3((unsigned)wgs), dim3(256), 0, as_stream(stream)>>>(
-      a, reinterpret_cast<const WgradTile*>(reinterpret_cast<char*>(workspace) + a.tiles_off));
+  tower_wgrad_kernel<<<dim3((unsigned)wgs), dim3(256), 0, as_stream(stream)>>>(a, wgrad_tiles(workspace, a));
   return check_launch("tower_wgrad_pre");
 }
 
-static int fused_wgrad_adagrad(const tt_tower_shape_t* shape, int64_t B, float* loss, void* workspace,
-                               size_t ws_bytes, const tt_table_meta_t* tables, int T,
-                               const tt_feature_meta_t* features, int F, int64_t emb_B, const float* grad,
-                               int64_t ldg, float* weights, float* state, float lr, float eps, void* dedup_ws,
-                               size_t dedup_ws_bytes, int64_t dedup_max_lookups, int64_t* adam_step_state,
-                               float adam_lr, float adam_beta1, float adam_beta2, void* stream) {
+static int fused_wgrad_adagrad(const tt_launch_plan_t& p, void* stream) {
   WgradArgs a{};
   int64_t wgs = 0;
-  int rc = wgrad_args(shape, B, loss, workspace, ws_bytes, a, &wgs);
+  TowerLayout L;
+  int rc = wgrad_args(p.shape, p.B, p.workspace, p.ws_bytes, p.wgrad, a, &wgs, L);
   if (rc) return rc;
-  if (adam_step_state) {  // T2 advances the Adam step and precomputes its scalars for T3
-    TowerLayout L;
-    tower_layout(shape, B, &L);
-    a.step_state = adam_step_state;
-    a.adam_pre = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + L.o_counter);
-    a.lr = adam_lr;
-    a.beta1 = adam_beta1;
-    a.beta2 = adam_beta2;
-  }
   DdUpdateArgs d{};
   int64_t dd_grid = 0;
-  rc = dedup_update_args(tables, T, features, F, emb_B, grad, ldg, weights, state, lr, eps, dedup_ws, dedup_ws_bytes,
-                         dedup_max_lookups, d, &dd_grid);
-  if (rc) return rc;
+  if ((rc = dedup_update_args(p.adagrad, d, &dd_grid))) return rc;
   if (wgs + dd_grid > INT32_MAX) return fail(TT_EINVAL, "tower_wgrad_rowwise_adagrad: grid too large");
   tower_wgrad_dedup_kernel<<<dim3((unsigned)(wgs + dd_grid)), dim3(256), 0, as_stream(stream)>>>(
-      a, reinterpret_cast<const WgradTile*>(reinterpret_cast<char*>(workspace) + a.tiles_off), d, (int)wgs);
+      a, wgrad_tiles(p.workspace, a), d, (int)wgs);
   return check_launch("tower_wgrad_rowwise_adagrad");
 }
 
-// T3 arguments (shared by every T3 launch form)
-static int t3_args(const tt_tower_shape_t* shape, int64_t B, float* params, float* exp_avg, float* exp_avg_sq,
-                   float lr, float beta1, float beta2, float eps, float weight_decay, int64_t* step_state, int do_adam,
-                   float* grads_out, const float* grads_in, void* workspace, size_t ws_bytes, const float* adam_pre,
-                   int out_copies, const int64_t* out_off, float out_scale, int in_srcs, int64_t in_stride,
-                   UpdateArgs& a, int64_t* grid) {
-  TowerLayout L;
-  int rc = tower_layout(shape, B, &L);
+// what a T3 launch takes beside its UPDATE role (named at each call site; declaration order)
+struct T3Opts {
+  int64_t* step_state = nullptr;     // Adam's step counter, advanced by T3 itself (tt_adam_step's) ...
+  float lr = 0.f;                    // ... and its learning rate
+  int do_adam = 0;
+  const float* grads_in = nullptr;   // the gradient to apply instead of T2's partials: in_srcs blocks,
+  int in_srcs = 1;                   // in_stride floats apart, summed in ascending order
+  int64_t in_stride = 0;
+  bool adam_pre = false;             // Adam's step scalars are in the workspace (a WGRAD role wrote them)
+  const DdUpdateArgs* dd = nullptr;  // the row-wise Adagrad update's workgroups in front (UPDATE | ADAGRAD)
+  int64_t dd_grid = 0;
+  const tt_peer_wait_t* wait = nullptr;
+};
+
+// the replicated form's output (UPDATE.replicated = 1): checked by its two launches before anything else
+static int replicated_check(const tt_update_role_t& u) {
+  if (!u.base || !u.offsets || u.copies < 1 || u.copies > 16) return fail(TT_EINVAL, "tower_grads_replicated: bad output");
+  return TT_OK;
+}
+
+// T3 arguments (shared by every T3 launch form); hands back the layout, *grid = T3's workgroup count
+static int t3_args(const tt_tower_shape_t* shape, int64_t B, void* workspace, size_t ws_bytes,
+                   const tt_update_role_t& u, const T3Opts& o, UpdateArgs& a, int64_t* grid, TowerLayout& L) {
+  int rc = tower_ws_layout(shape, B, workspace, ws_bytes, &L);
   if (rc) return rc;
-  if (!workspace || ws_bytes < L.total) return fail(TT_ECAPACITY, "tower: workspace too small");
-  if (!params || (do_adam && (!exp_avg || !exp_avg_sq || (!step_state && !adam_pre))))
+  const bool rep = u.replicated != 0;  // no Adam: the gradient x scale to base + offsets[q]
+  if (!u.params || (o.do_adam && (!u.exp_avg || !u.exp_avg_sq || (!o.step_state && !o.adam_pre))))
     return fail(TT_EINVAL, "tower: null pointer");
-  if (out_copies > 16) return fail(TT_EINVAL, "tower: at most 16 gradient copies");
+  if (rep && u.copies > 16) return fail(TT_EINVAL, "tower: at most 16 gradient copies");
   char* ws = reinterpret_cast<char*>(workspace);
   a = UpdateArgs{};
-  a.params = params;
-  a.exp_avg = exp_avg;
-  a.exp_avg_sq = exp_avg_sq;
+  a.params = u.params;
+  a.exp_avg = rep ? nullptr : u.exp_avg;
+  a.exp_avg_sq = rep ? nullptr : u.exp_avg_sq;
   a.slab = reinterpret_cast<const float*>(ws + L.o_slab);
   a.dbpart = reinterpret_cast<const float*>(ws + L.o_dbpart);
   a.P = L.P;
@@ -3366,46 +3396,42 @@ static int t3_args(const tt_tower_shape_t* shape, int64_t B, float* params, floa
   // launch_t1 uses for shapes other than two layers over inputs <= 128 wide
   a.skip_plain = shape->L == 2 && shape->in_dim[0] <= 128 && shape->in_dim[1] <= 128 &&
                  !(shape->flags & TT_TOWER_GENERAL_T1);
-  a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.wd = weight_decay;
-  a.step_state = step_state;
-  a.do_adam = do_adam;
-  a.grads_out = grads_out;
-  a.grads_in = grads_in;
-  a.adam_pre = adam_pre;
-  a.out_copies = out_copies;
-  for (int q = 0; q < out_copies && out_off; ++q) a.out_off[q] = out_off[q];
-  a.out_scale = out_scale;
-  a.in_srcs = in_srcs;
-  a.in_stride = in_stride;
+  a.lr = o.lr;
+  // (the replicated form reads none of Adam's constants: fixed values, whatever the role holds)
+  a.beta1 = rep ? 0.9f : u.beta1; a.beta2 = rep ? 0.999f : u.beta2; a.eps = rep ? 1e-8f : u.eps;
+  a.wd = rep ? 0.f : u.weight_decay;
+  a.step_state = o.step_state;
+  a.do_adam = o.do_adam;
+  a.grads_out = rep ? u.base : u.grads_out;
+  a.grads_in = o.grads_in;
+  a.adam_pre = o.adam_pre ? reinterpret_cast<const float*>(ws + L.o_counter) : nullptr;
+  // one copy takes the multi-copy path too (scale applied): give it two identical copies
+  a.out_copies = !rep ? 1 : u.copies == 1 ? 2 : u.copies;
+  for (int q = 0; rep && u.offsets && q < a.out_copies; ++q) a.out_off[q] = u.offsets[q < u.copies ? q : 0];
+  a.out_scale = rep ? u.scale : 1.f;
+  a.in_srcs = o.in_srcs;
+  a.in_stride = o.in_stride;
   *grid = ceil_div(L.P, 256);
   return TT_OK;
 }
 
-static int launch_t3(const tt_tower_shape_t* shape, int64_t B, float* params, float* exp_avg, float* exp_avg_sq,
-                     float lr, float beta1, float beta2, float eps, float weight_decay, int64_t* step_state,
-                     int do_adam, float* grads_out, const float* grads_in, void* workspace, size_t ws_bytes,
-                     void* stream, const float* adam_pre = nullptr, const DdUpdateArgs* dd = nullptr,
-                     int64_t dd_grid = 0, int out_copies = 1, const int64_t* out_off = nullptr,
-                     float out_scale = 1.f, int in_srcs = 1, int64_t in_stride = 0,
-                     const tt_peer_wait_t* wait = nullptr) {
+static int launch_t3(const tt_tower_shape_t* shape, int64_t B, void* workspace, size_t ws_bytes,
+                     const tt_update_role_t& u, const T3Opts& o, void* stream) {
   UpdateArgs a;
   int64_t g3 = 0;
-  int rc = t3_args(shape, B, params, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step_state, do_adam,
-                   grads_out, grads_in, workspace, ws_bytes, adam_pre, out_copies, out_off, out_scale, in_srcs,
-                   in_stride, a, &g3);
+  TowerLayout L;
+  int rc = t3_args(shape, B, workspace, ws_bytes, u, o, a, &g3, L);
   if (rc) return rc;
-  if ((rc = peer_wait_args(wait, a.wt, "tower_update"))) return rc;
-  if (dd) {
-    if (dd_grid + g3 > INT32_MAX) return fail(TT_EINVAL, "tower_update_rowwise_adagrad: grid too large");
-    tower_update_dedup_kernel<<<dim3((unsigned)(dd_grid + g3)), dim3(256), 0, as_stream(stream)>>>(a, *dd, (int)dd_grid);
+  if ((rc = peer_wait_args(o.wait, a.wt, "tower_update"))) return rc;
+  if (o.dd) {
+    if (o.dd_grid + g3 > INT32_MAX) return fail(TT_EINVAL, "tower_update_rowwise_adagrad: grid too large");
+    tower_update_dedup_kernel<<<dim3((unsigned)(o.dd_grid + g3)), dim3(256), 0, as_stream(stream)>>>(a, *o.dd,
+                                                                                                      (int)o.dd_grid);
     return check_launch("tower_update_rowwise_adagrad");
   }
 #if TT_EXPERIMENTS
-  if (getenv("TT_RING_STAMPS")) {  // workgroups [0, 512) stamp
-    TowerLayout L;
-    tower_layout(shape, B, &L);
+  if (getenv("TT_RING_STAMPS"))  // workgroups [0, 512) stamp
     a.stamps = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace) + L.o_dbg) + 6144;
-  }
 #endif
   int bs = 256;
 #if TT_EXPERIMENTS
@@ -3415,68 +3441,60 @@ static int launch_t3(const tt_tower_shape_t* shape, int64_t B, float* params, fl
   return check_launch("tower_update");
 }
 
+// the Adam form of the UPDATE role from an export's arguments
+static tt_update_role_t adam_role(float* params, float* exp_avg, float* exp_avg_sq, float eps, float beta1,
+                                  float beta2, float weight_decay, float* grads_out) {
+  tt_update_role_t u{};
+  u.params = params, u.exp_avg = exp_avg, u.exp_avg_sq = exp_avg_sq;
+  u.eps = eps, u.beta1 = beta1, u.beta2 = beta2, u.weight_decay = weight_decay, u.grads_out = grads_out;
+  return u;
+}
+
 int tt_tower_update(const tt_tower_shape_t* shape, int64_t B, float* params, float* exp_avg, float* exp_avg_sq,
                     float lr, float beta1, float beta2, float eps, float weight_decay, int64_t* step_state,
                     int do_adam, float* grads_out, void* workspace, size_t ws_bytes, void* stream) {
-  return launch_t3(shape, B, params, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step_state, do_adam,
-                   grads_out, nullptr, workspace, ws_bytes, stream);
+  return launch_t3(shape, B, workspace, ws_bytes,
+                   adam_role(params, exp_avg, exp_avg_sq, eps, beta1, beta2, weight_decay, grads_out),
+                   {.step_state = step_state, .lr = lr, .do_adam = do_adam}, stream);
 }
 
 int tt_tower_update_pre(const tt_tower_shape_t* shape, int64_t B, float* params, float* exp_avg, float* exp_avg_sq,
                         float eps, float beta1, float beta2, float weight_decay, float* grads_out, void* workspace,
                         size_t ws_bytes, void* stream) {
-  TowerLayout L;
-  int rc = tower_layout(shape, B, &L);
-  if (rc) return rc;
-  if (!workspace || ws_bytes < L.total) return fail(TT_ECAPACITY, "tower: workspace too small");
-  const float* pre = reinterpret_cast<const float*>(reinterpret_cast<const char*>(workspace) + L.o_counter);
-  return launch_t3(shape, B, params, exp_avg, exp_avg_sq, 0.f, beta1, beta2, eps, weight_decay, nullptr, 1, grads_out,
-                   nullptr, workspace, ws_bytes, stream, pre);
+  return launch_t3(shape, B, workspace, ws_bytes,
+                   adam_role(params, exp_avg, exp_avg_sq, eps, beta1, beta2, weight_decay, grads_out),
+                   {.do_adam = 1, .adam_pre = true}, stream);
 }
 
-static int fused_update_adagrad(const tt_tower_shape_t* shape, int64_t B, float* params, float* exp_avg,
-                                float* exp_avg_sq, float eps, float beta1, float beta2, float weight_decay,
-                                float* grads_out, void* workspace, size_t ws_bytes,
-                                const tt_table_meta_t* tables, int T, const tt_feature_meta_t* features, int F,
-                                int64_t emb_B, const float* grad, int64_t ldg, float* weights, float* state,
-                                float lr, float emb_eps, void* dedup_ws, size_t dedup_ws_bytes,
-                                int64_t dedup_max_lookups, void* stream) {
+static int fused_update_adagrad(const tt_launch_plan_t& p, void* stream) {
+  // the towers' checks come before the ADAGRAD role's (launch_t3 repeats them, at no cost that matters)
   TowerLayout L;
-  int rc = tower_layout(shape, B, &L);
+  int rc = tower_ws_layout(p.shape, p.B, p.workspace, p.ws_bytes, &L);
   if (rc) return rc;
-  if (!workspace || ws_bytes < L.total) return fail(TT_ECAPACITY, "tower: workspace too small");
   DdUpdateArgs d{};
   int64_t dd_grid = 0;
-  rc = dedup_update_args(tables, T, features, F, emb_B, grad, ldg, weights, state, lr, emb_eps, dedup_ws,
-                         dedup_ws_bytes, dedup_max_lookups, d, &dd_grid);
-  if (rc) return rc;
-  const float* pre = reinterpret_cast<const float*>(reinterpret_cast<const char*>(workspace) + L.o_counter);
-  return launch_t3(shape, B, params, exp_avg, exp_avg_sq, 0.f, beta1, beta2, eps, weight_decay, nullptr, 1, grads_out,
-                   nullptr, workspace, ws_bytes, stream, pre, &d, dd_grid);
+  if ((rc = dedup_update_args(p.adagrad, d, &dd_grid))) return rc;
+  return launch_t3(p.shape, p.B, p.workspace, p.ws_bytes, p.update,
+                   {.do_adam = 1, .adam_pre = true, .dd = &d, .dd_grid = dd_grid}, stream);
 }
 
 int tt_tower_adam_grads(const tt_tower_shape_t* shape, int64_t B, float* params, const float* grads,
                         float* exp_avg, float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
                         float weight_decay, int64_t* step_state, void* workspace, size_t ws_bytes, void* stream) {
   if (!grads) return fail(TT_EINVAL, "tower_adam_grads: null gradient");
-  return launch_t3(shape, B, params, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step_state, 1,
-                   nullptr, grads, workspace, ws_bytes, stream);
+  return launch_t3(shape, B, workspace, ws_bytes,
+                   adam_role(params, exp_avg, exp_avg_sq, eps, beta1, beta2, weight_decay, nullptr),
+                   {.step_state = step_state, .lr = lr, .do_adam = 1, .grads_in = grads}, stream);
 }
 
 int tt_tower_grads_replicated(const tt_tower_shape_t* shape, int64_t B, float* params, float* base, int copies,
                               const int64_t* offsets, float scale, void* workspace, size_t ws_bytes, void* stream) {
-  TowerLayout L;
-  int rc = tower_layout(shape, B, &L);
-  if (rc) return rc;
-  if (!base || !offsets || copies < 1 || copies > 16) return fail(TT_EINVAL, "tower_grads_replicated: bad output");
+  tt_update_role_t u{};
+  u.params = params, u.replicated = 1, u.copies = copies, u.base = base, u.offsets = offsets, u.scale = scale;
+  if (int rc = replicated_check(u)) return rc;
   for (int q = 0; q < copies; ++q)
     if (offsets[q] < 0) return fail(TT_EINVAL, "tower_grads_replicated: negative offset");
-  int64_t off[16];
-  for (int q = 0; q < copies; ++q) off[q] = offsets[q];
-  if (copies == 1) off[1] = off[0];
-  // copies == 1 takes the multi-copy path too (scale applied): give it two identical copies
-  return launch_t3(shape, B, params, nullptr, nullptr, 0.f, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, 0, base, nullptr,
-                   workspace, ws_bytes, stream, nullptr, nullptr, 0, copies == 1 ? 2 : copies, off, scale);
+  return launch_t3(shape, B, workspace, ws_bytes, u, {}, stream);
 }
 
 int tt_tower_adam_pre_grads_sum(const tt_tower_shape_t* shape, int64_t B, float* params, const float* grads, int nsrc,
@@ -3484,99 +3502,44 @@ int tt_tower_adam_pre_grads_sum(const tt_tower_shape_t* shape, int64_t B, float*
                                 float beta2, float weight_decay, void* workspace, size_t ws_bytes,
                                 const tt_peer_wait_t* wait, void* stream) {
   TowerLayout L;
-  int rc = tower_layout(shape, B, &L);
+  int rc = tower_ws_layout(shape, B, workspace, ws_bytes, &L);
   if (rc) return rc;
-  if (!workspace || ws_bytes < L.total) return fail(TT_ECAPACITY, "tower: workspace too small");
   if (!grads || nsrc < 1 || (nsrc > 1 && src_stride < L.P)) return fail(TT_EINVAL, "tower_adam_pre_grads_sum: bad gradient");
   if (wait && wait->W != nsrc) return fail(TT_EINVAL, "tower_adam_pre_grads_sum: wait.W must be nsrc");
-  const float* pre = reinterpret_cast<const float*>(reinterpret_cast<const char*>(workspace) + L.o_counter);
-  return launch_t3(shape, B, params, exp_avg, exp_avg_sq, 0.f, beta1, beta2, eps, weight_decay, nullptr, 1, nullptr,
-                   grads, workspace, ws_bytes, stream, pre, nullptr, 0, 1, nullptr, 1.f, nsrc, src_stride, wait);
+  return launch_t3(shape, B, workspace, ws_bytes,
+                   adam_role(params, exp_avg, exp_avg_sq, eps, beta1, beta2, weight_decay, nullptr),
+                   {.do_adam = 1, .grads_in = grads, .in_srcs = nsrc, .in_stride = src_stride, .adam_pre = true,
+                    .wait = wait},
+                   stream);
 }
 
 }  // extern "C"
 
 namespace tt {
-// shared by the two fused entry points: the next batch's route arguments (as tt_shard_route_segs)
-static int route_segs_args(int F, int64_t B, const void* const* cols, int id_dtype, const int64_t* num_embeddings,
-                           const int64_t* block_sizes, const int32_t* owners, int W, const tt_shard_seg_t* segs,
-                           int64_t* send, int32_t* pos_in, int32_t* pos_out, int32_t* overflow, void* route_ws,
-                           size_t route_ws_bytes, RouteArgs& a) {
-  if (F < 1 || F > TT_MAX_FEATURES || W < 1 || W > RT_MAXW || B < 1) return fail(TT_EINVAL, "route: bad sizes");
-  if (id_dtype != TT_I32 && id_dtype != TT_I64) return fail(TT_EINVAL, "route: ids must be int32/int64");
-  if (!cols || !num_embeddings || !block_sizes || !owners || !segs || !send || !pos_in || !pos_out || !overflow)
-    return fail(TT_EINVAL, "route: null pointer");
-  if (!route_ws || route_ws_bytes < tt_shard_route_workspace_bytes(F, B))
-    return fail(TT_ECAPACITY, "route: workspace too small");
-  for (int f = 0; f < F; ++f) {
-    if (!cols[f] || num_embeddings[f] < 1) return fail(TT_EINVAL, "route: bad column");
-    if (block_sizes[f] < 0 || (block_sizes[f] == 0 && (owners[f] < 0 || owners[f] >= W)))
-      return fail(TT_EINVAL, "route: bad sharding of a feature");
-    if (block_sizes[f] > 0 && (num_embeddings[f] + block_sizes[f] - 1) / block_sizes[f] > W)
-      return fail(TT_EINVAL, "route: row blocks exceed the rank count");
-    if ((block_sizes[f] > 0 ? block_sizes[f] : num_embeddings[f]) >= (1ll << DD_TABLE_SHIFT))
-      return fail(TT_EINVAL, "route: local rows >= 2^40");
-    a.col[f] = cols[f];
-    a.num_emb[f] = num_embeddings[f];
-    a.block[f] = block_sizes[f];
-    a.owner[f] = owners[f];
-  }
-  a.id_dtype = id_dtype;
-  a.F = F;
-  a.W = W;
-  a.B = B;
-  a.C = 1;
-  a.nblk = (int)ceil_div(B, RT_BLOCK);
-  a.send = send;
-  a.pos = pos_in;
-  a.pos_out = pos_out;
-  a.segs = segs;
-  a.overflow = overflow;
-  char* ws = reinterpret_cast<char*>(route_ws);
-  a.dl = reinterpret_cast<int64_t*>(ws);
-  a.cnt = reinterpret_cast<int32_t*>(ws + align_up(sizeof(int64_t) * (size_t)F * (size_t)B, 256));
-  return TT_OK;
+// the next batch's route of the fused launches (as tt_shard_route_segs; never an empty batch)
+static int fused_route_args(const tt_launch_plan_t& p, RouteArgs& r) {
+  if (p.B < 1) return fail(TT_EINVAL, "route: bad batch / segment capacity");
+  return route_args(p.route, p.B, RT_SEGS, "route", r);
 }
 }  // namespace tt
 
 extern "C" {
 
-static int fused_wgrad_route_count_adagrad(const tt_tower_shape_t* shape, int64_t B, float* loss, void* workspace,
-                                           size_t ws_bytes, int64_t* adam_step_state, float adam_lr,
-                                           float adam_beta1, float adam_beta2, int F, const void* const* cols,
-                                           int id_dtype,
-                                           const int64_t* num_embeddings, const int64_t* block_sizes,
-                                           const int32_t* owners, int W, const tt_shard_seg_t* segs, int64_t* send,
-                                           int32_t* pos_in, int32_t* pos_out, int32_t* overflow, void* route_ws,
-                                           size_t route_ws_bytes, const tt_table_meta_t* tables, int T,
-                                           const tt_feature_meta_t* features, int Fsrc, int64_t emb_B,
-                                           const float* emb_grad, int64_t ldg, float* weights, float* state,
-                                           float emb_lr, float emb_eps, void* dedup_ws, size_t dedup_ws_bytes,
-                                           int64_t dedup_max_lookups, const tt_peer_wait_t* wait, void* stream) {
-  if (!adam_step_state) return fail(TT_EINVAL, "tower_wgrad_route_rowwise: null Adam step state");
+static int fused_wgrad_route_count_adagrad(const tt_launch_plan_t& p, void* stream) {
+  if (!p.wgrad.adam_step_state) return fail(TT_EINVAL, "tower_wgrad_route_rowwise: null Adam step state");
   PxWait pw;
-  if (int rc = peer_wait_args(wait, pw, "tower_wgrad_route_rowwise")) return rc;
+  if (int rc = peer_wait_args(p.wait, pw, "tower_wgrad_route_rowwise")) return rc;
   WgradArgs a{};
   int64_t wgs = 0;
-  int rc = wgrad_args(shape, B, loss, workspace, ws_bytes, a, &wgs);
-  if (rc) return rc;
   TowerLayout L;
-  tower_layout(shape, B, &L);
-  a.step_state = adam_step_state;  // the loss wave advances Adam's step and writes its scalars
-  a.adam_pre = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + L.o_counter);
-  a.lr = adam_lr;
-  a.beta1 = adam_beta1;
-  a.beta2 = adam_beta2;
-  RouteArgs r{};
-  rc = route_segs_args(F, B, cols, id_dtype, num_embeddings, block_sizes, owners, W, segs, send, pos_in, pos_out,
-                       overflow, route_ws, route_ws_bytes, r);
+  int rc = wgrad_args(p.shape, p.B, p.workspace, p.ws_bytes, p.wgrad, a, &wgs, L);
   if (rc) return rc;
+  RouteArgs r{};
+  if ((rc = fused_route_args(p, r))) return rc;
   DdUpdateArgs d{};
   int64_t dd_grid = 0;
-  rc = dedup_update_args(tables, T, features, Fsrc, emb_B, emb_grad, ldg, weights, state, emb_lr, emb_eps, dedup_ws,
-                         dedup_ws_bytes, dedup_max_lookups, d, &dd_grid);
-  if (rc) return rc;
-  const int64_t n_cnt = (int64_t)r.nblk * F;
+  if ((rc = dedup_update_args(p.adagrad, d, &dd_grid))) return rc;
+  const int64_t n_cnt = (int64_t)r.nblk * r.F;
   if (wgs + n_cnt + dd_grid > INT32_MAX) return fail(TT_EINVAL, "tower_wgrad_route_rowwise: grid too large");
   d.xcd = d.hot_wgs % 8 == 0 ? 1 : 0;  // the owner's update workgroups first (dd_first): slot role aligned
 #if TT_EXPERIMENTS
@@ -3585,34 +3548,22 @@ static int fused_wgrad_route_count_adagrad(const tt_tower_shape_t* shape, int64_
   constexpr bool dd_first = true;
 #endif
   tower_wgrad_route_rowwise_kernel<<<dim3((unsigned)(wgs + n_cnt + dd_grid)), dim3(256), 0, as_stream(stream)>>>(
-      a, reinterpret_cast<const WgradTile*>(reinterpret_cast<char*>(workspace) + a.tiles_off), r, d, (int)wgs,
-      (int)n_cnt, dd_first ? (int)dd_grid : 0, pw);
+      a, wgrad_tiles(p.workspace, a), r, d, (int)wgs, (int)n_cnt, dd_first ? (int)dd_grid : 0, pw);
   return check_launch("tower_wgrad_route_count_rowwise_adagrad");
 }
 
-static int fused_route_count_adagrad(int F, int64_t B, const void* const* cols, int id_dtype,
-                                     const int64_t* num_embeddings, const int64_t* block_sizes,
-                                     const int32_t* owners, int W, const tt_shard_seg_t* segs, int64_t* send,
-                                     int32_t* pos_in, int32_t* pos_out, int32_t* overflow, void* route_ws,
-                                     size_t route_ws_bytes, const tt_table_meta_t* tables, int T,
-                                     const tt_feature_meta_t* features, int Fsrc, int64_t emb_B,
-                                     const float* emb_grad, int64_t ldg, float* weights, float* state,
-                                     float emb_lr, float emb_eps, void* dedup_ws, size_t dedup_ws_bytes,
-                                     int64_t dedup_max_lookups, const tt_peer_wait_t* wait, void* stream) {
+static int fused_route_count_adagrad(const tt_launch_plan_t& p, void* stream) {
   PxWait pw;
-  if (int rc = peer_wait_args(wait, pw, "shard_route_count_rowwise_adagrad")) return rc;
+  if (int rc = peer_wait_args(p.wait, pw, "shard_route_count_rowwise_adagrad")) return rc;
   // launch U of the pipelined sharded step without its T2 tiles (those run on a parallel branch of
   // the step graph, beside exchange A): the owner's update workgroups first, then the route count
   RouteArgs r{};
-  int rc = route_segs_args(F, B, cols, id_dtype, num_embeddings, block_sizes, owners, W, segs, send, pos_in, pos_out,
-                           overflow, route_ws, route_ws_bytes, r);
+  int rc = fused_route_args(p, r);
   if (rc) return rc;
   DdUpdateArgs d{};
   int64_t dd_grid = 0;
-  rc = dedup_update_args(tables, T, features, Fsrc, emb_B, emb_grad, ldg, weights, state, emb_lr, emb_eps, dedup_ws,
-                         dedup_ws_bytes, dedup_max_lookups, d, &dd_grid);
-  if (rc) return rc;
-  const int64_t n_cnt = (int64_t)r.nblk * F;
+  if ((rc = dedup_update_args(p.adagrad, d, &dd_grid))) return rc;
+  const int64_t n_cnt = (int64_t)r.nblk * r.F;
   if (n_cnt + dd_grid > INT32_MAX) return fail(TT_EINVAL, "shard_route_count_rowwise_adagrad: grid too large");
   d.xcd = d.hot_wgs % 8 == 0 ? 1 : 0;  // the owner's update workgroups first: slot role aligned
   WgradArgs a{};
@@ -3621,47 +3572,19 @@ static int fused_route_count_adagrad(int F, int64_t B, const void* const* cols, 
   return check_launch("shard_route_count_rowwise_adagrad");
 }
 
-static int fused_grads_route_place_gather(const tt_tower_shape_t* shape, int64_t B, float* params, float* base,
-                                          int copies, const int64_t* offsets, float scale, void* workspace,
-                                          size_t ws_bytes, int F, const void* const* cols, int id_dtype,
-                                          const int64_t* num_embeddings, const int64_t* block_sizes,
-                                          const int32_t* owners, int W, const tt_shard_seg_t* segs,
-                                          int64_t* send, int32_t* pos_in, int32_t* pos_out, int32_t* overflow,
-                                          void* route_ws, size_t route_ws_bytes, const float* weights,
-                                          const tt_table_meta_t* tables, int T, const int64_t* recv,
-                                          int64_t block_i64, int64_t counts_i64, const int64_t* seg_off,
-                                          int64_t slots, void* rows_out, int64_t out_stride, int32_t* bad,
-                                          void* dedup_ws, size_t dedup_ws_bytes, int64_t dedup_max_lookups,
-                                          const tt_peer_direct_t* direct, void* stream) {
-  if (!params || !base || !offsets || copies < 1 || copies > 16) return fail(TT_EINVAL, "tower_grads_replicated: bad output");
+static int fused_grads_route_place_gather(const tt_launch_plan_t& p, void* stream) {
+  if (!p.update.params) return fail(TT_EINVAL, "tower_grads_replicated: bad output");
+  int rc = replicated_check(p.update);
+  if (rc) return rc;
   RouteArgs r{};
-  int rc = route_segs_args(F, B, cols, id_dtype, num_embeddings, block_sizes, owners, W, segs, send, pos_in, pos_out,
-                           overflow, route_ws, route_ws_bytes, r);
-  if (rc) return rc;
+  if ((rc = fused_route_args(p, r))) return rc;
   GatherSegArgs g{};
-  rc = gather_segs_args(weights, tables, T, F, W, recv, block_i64, counts_i64, seg_off, slots, rows_out, out_stride,
-                        bad, dedup_ws, dedup_ws_bytes, dedup_max_lookups, g);
-  if (rc) return rc;
-  if (direct) {
-    if ((rc = peer_direct_check(*direct, "tower_grads_place_gather"))) return rc;
-    if (direct->W != W) return fail(TT_EINVAL, "tower_grads_place_gather: direct.W must be the route's W");
-    for (int s = 0; s < W; ++s) {
-      if (direct->first_row[s] != (int64_t)s * out_stride)
-        return fail(TT_EINVAL, "tower_grads_place_gather: direct.first_row[s] must be s * out_stride");
-      g.dblk[s] = reinterpret_cast<__bf16*>(direct->row0[s]);
-    }
-    g.dW = W;
-    g.epoch = direct->epoch;
-  }
-  int64_t off[16];
-  for (int q = 0; q < copies; ++q) off[q] = offsets[q];
-  if (copies == 1) off[1] = off[0];  // one copy takes the multi-copy path too (scale applied)
+  if ((rc = gather_segs_args(p.gather, r.F, r.W, g))) return rc;
   UpdateArgs a;
   int64_t g3 = 0;
-  rc = t3_args(shape, B, params, nullptr, nullptr, 0.f, 0.9f, 0.999f, 1e-8f, 0.f, nullptr, 0, base, nullptr, workspace,
-               ws_bytes, nullptr, copies == 1 ? 2 : copies, off, scale, 1, 0, a, &g3);
-  if (rc) return rc;
-  const int64_t n_place = (int64_t)r.nblk * F, n_gather = ceil_div(ceil_div((int64_t)W * slots, GS_SL), 8);
+  TowerLayout L;
+  if ((rc = t3_args(p.shape, p.B, p.workspace, p.ws_bytes, p.update, {}, a, &g3, L))) return rc;
+  const int64_t n_place = (int64_t)r.nblk * r.F, n_gather = ceil_div(ceil_div((int64_t)r.W * g.S, GS_SL), 8);
   if (g3 + n_place + n_gather > INT32_MAX) return fail(TT_EINVAL, "tower_grads_place_gather: grid too large");
   tower_grads_place_gather_kernel<<<dim3((unsigned)(g3 + n_place + n_gather)), dim3(256), 0, as_stream(stream)>>>(
       a, r, g, (int)g3, (int)n_place);
@@ -3677,9 +3600,7 @@ int tt_tower_fwd_bwd_gather_update(const tt_tower_shape_t* shape, int64_t B, con
   if (!cols || !num_embeddings || !table_rows || !table_state || !dedup_ws)
     return fail(TT_EINVAL, "tower_gather_update: null pointer");
   if (id_dtype != TT_I32 && id_dtype != TT_I64) return fail(TT_EINVAL, "tower_gather_update: ids must be int32/int64");
-  if (dedup_max_lookups < 2 * B || dedup_max_lookups >= (int64_t)DD_CNT_MASK ||
-      dedup_ws_bytes < dedup_layout(nullptr, dedup_max_lookups, nullptr) || (reinterpret_cast<uintptr_t>(dedup_ws) & 63))
-    return fail(TT_ECAPACITY, "tower_gather_update: dedup workspace too small / misaligned");
+  if (int rc = check_dedup_ws(dedup_ws, dedup_ws_bytes, dedup_max_lookups, 2 * B, "tower_gather_update", true)) return rc;
   TowerArgs a{};
   for (int t = 0; t < 2; ++t) {
     if (!cols[t] || !table_rows[t] || !table_state[t] || num_embeddings[t] < 1)
@@ -3700,112 +3621,67 @@ int tt_tower_fwd_bwd_gather_update(const tt_tower_shape_t* shape, int64_t B, con
   a.ulr = lr;
   a.ueps = eps;
   dedup_layout(dedup_ws, dedup_max_lookups, &a.dd);
-  return launch_t1(shape, B, a, nullptr, ldp, gpooled, params, labels, label_dtype, grad_scale, logits, workspace,
-                   ws_bytes, stream);
+  return launch_t1(shape, B, a, nullptr, ldp, gpooled,
+                   {params, labels, label_dtype, grad_scale, logits, workspace, ws_bytes, stream});
 }
 
-static int fused_wgrad_insert(const tt_tower_shape_t* shape, int64_t B, float* loss, void* workspace, size_t ws_bytes,
-                              int64_t* adam_step_state, float adam_lr, float adam_beta1, float adam_beta2,
-                              const void* const* next_cols, int id_dtype, const int64_t* num_embeddings,
-                              const int32_t* dedup_tables, void* next_dedup_ws, size_t dedup_ws_bytes,
-                              int64_t dedup_max_lookups, void* stream) {
-  if (!adam_step_state || !next_cols || !num_embeddings || !dedup_tables || !next_dedup_ws)
-    return fail(TT_EINVAL, "tower_wgrad_pre_insert: null pointer");
-  if (id_dtype != TT_I32 && id_dtype != TT_I64) return fail(TT_EINVAL, "tower_wgrad_pre_insert: ids must be int32/int64");
-  if (dedup_max_lookups < 2 * B || dedup_max_lookups >= (int64_t)DD_CNT_MASK ||
-      dedup_ws_bytes < dedup_layout(nullptr, dedup_max_lookups, nullptr) ||
-      (reinterpret_cast<uintptr_t>(next_dedup_ws) & 63))
-    return fail(TT_ECAPACITY, "tower_wgrad_pre_insert: dedup workspace too small / misaligned");
+static int fused_wgrad_insert(const tt_launch_plan_t& p, void* stream) {
+  if (!p.wgrad.adam_step_state) return fail(TT_EINVAL, "tower_wgrad_pre_insert: null pointer");
+  InsertArgs ins{};
+  int rc = insert_args(p.insert, p.B, "tower_wgrad_pre_insert", ins);
+  if (rc) return rc;
   WgradArgs a{};
   int64_t wgs = 0;
-  int rc = wgrad_args(shape, B, loss, workspace, ws_bytes, a, &wgs);
-  if (rc) return rc;
   TowerLayout L;
-  tower_layout(shape, B, &L);
-  a.step_state = adam_step_state;
-  a.adam_pre = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + L.o_counter);
-  a.lr = adam_lr;
-  a.beta1 = adam_beta1;
-  a.beta2 = adam_beta2;
-  InsertArgs ins{};
-  rc = insert_args(B, next_cols, id_dtype, num_embeddings, dedup_tables, next_dedup_ws, dedup_max_lookups, ins);
-  if (rc) return rc;
-  const int64_t n_ins = ceil_div(ceil_div(2 * B, 64), 4);  // 4 waves of 64 lookups per workgroup
-  int64_t* stamps = TT_EXPERIMENTS && getenv("TT_RING_STAMPS") ? reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace) + L.o_dbg) + 4096 : nullptr;
+  if ((rc = wgrad_args(p.shape, p.B, p.workspace, p.ws_bytes, p.wgrad, a, &wgs, L))) return rc;
+  const int64_t n_ins = ceil_div(ceil_div(2 * p.B, 64), 4);  // 4 waves of 64 lookups per workgroup
+  int64_t* stamps = TT_EXPERIMENTS && getenv("TT_RING_STAMPS") ? reinterpret_cast<int64_t*>(reinterpret_cast<char*>(p.workspace) + L.o_dbg) + 4096 : nullptr;
   tower_wgrad_insert_kernel<<<dim3((unsigned)(wgs + n_ins)), dim3(256), 0, as_stream(stream)>>>(
-      a, reinterpret_cast<const WgradTile*>(reinterpret_cast<char*>(workspace) + a.tiles_off), ins, (int)wgs, stamps);
+      a, wgrad_tiles(p.workspace, a), ins, (int)wgs, stamps);
   return check_launch("tower_wgrad_pre_insert");
 }
 
-static int fused_update_adagrad_resolve(const tt_tower_shape_t* shape, int64_t B, float* params,
-                                        float* exp_avg, float* exp_avg_sq, float eps, float beta1,
-                                        float beta2, float weight_decay, float* grads_out, void* workspace,
-                                        size_t ws_bytes, const tt_table_meta_t* tables, int T,
-                                        const tt_feature_meta_t* features, int F, int64_t emb_B,
-                                        const float* grad, int64_t ldg, float* weights, float* state,
-                                        float lr, float emb_eps, void* dedup_ws, void* next_dedup_ws,
-                                        size_t dedup_ws_bytes, int64_t dedup_max_lookups, void* stream) {
+static int fused_update_adagrad_resolve(const tt_launch_plan_t& p, void* stream) {
+  void* next_dedup_ws = p.resolve.dedup_ws;  // bytes / max lookups: the ADAGRAD role's
   if (!next_dedup_ws || (reinterpret_cast<uintptr_t>(next_dedup_ws) & 63))
     return fail(TT_EINVAL, "tower_update_resolve: next dedup workspace null / misaligned");
   DdUpdateArgs d{};
   int64_t dd_grid = 0;
-  int rc = dedup_update_args(tables, T, features, F, emb_B, grad, ldg, weights, state, lr, emb_eps, dedup_ws,
-                             dedup_ws_bytes, dedup_max_lookups, d, &dd_grid);
+  int rc = dedup_update_args(p.adagrad, d, &dd_grid);
   if (rc) return rc;
   d.skip_single = 1;
   DedupWs next;
-  dedup_layout(next_dedup_ws, dedup_max_lookups, &next);
-  TowerLayout L;
-  rc = tower_layout(shape, B, &L);
-  if (rc) return rc;
-  const float* pre = reinterpret_cast<const float*>(reinterpret_cast<const char*>(workspace) + L.o_counter);
+  dedup_layout(next_dedup_ws, p.adagrad.dedup_max_lookups, &next);
   UpdateArgs a;
   int64_t g3 = 0;
-  rc = t3_args(shape, B, params, exp_avg, exp_avg_sq, 0.f, beta1, beta2, eps, weight_decay, nullptr, 1, grads_out,
-               nullptr, workspace, ws_bytes, pre, 1, nullptr, 1.f, 1, 0, a, &g3);
-  if (rc) return rc;
-  int64_t* stamps = TT_EXPERIMENTS && getenv("TT_RING_STAMPS") ? reinterpret_cast<int64_t*>(reinterpret_cast<char*>(workspace) + L.o_dbg) + 6144 : nullptr;
+  TowerLayout L;
+  if ((rc = t3_args(p.shape, p.B, p.workspace, p.ws_bytes, p.update, {.do_adam = 1, .adam_pre = true}, a, &g3, L)))
+    return rc;
+  int64_t* stamps = TT_EXPERIMENTS && getenv("TT_RING_STAMPS") ? reinterpret_cast<int64_t*>(reinterpret_cast<char*>(p.workspace) + L.o_dbg) + 6144 : nullptr;
   if (stamps && (K3_RES_WGS + dd_grid + g3 > 1024 || L.nwg > 256)) stamps = nullptr;
   tower_update_dedup_resolve_kernel<<<dim3((unsigned)(K3_RES_WGS + dd_grid + g3)), dim3(256), 0,
                                       as_stream(stream)>>>(a, d, next, (int)dd_grid, stamps);
   return check_launch("tower_update_pre_rowwise_adagrad_resolve");
 }
 
-static int fused_wgrad_insert_adagrad(const tt_tower_shape_t* shape, int64_t B, float* loss, void* workspace,
-                                      size_t ws_bytes, int64_t* adam_step_state, float adam_lr,
-                                      float adam_beta1, float adam_beta2, const void* const* next_cols,
-                                      int id_dtype, const int64_t* num_embeddings, const int32_t* dedup_tables,
-                                      const tt_table_meta_t* tables, int T, const tt_feature_meta_t* features,
-                                      int F, const float* grad, int64_t ldg, float* weights, float* state,
-                                      float lr, float emb_eps, void* dedup_ws, void* next_dedup_ws,
-                                      size_t dedup_ws_bytes, int64_t dedup_max_lookups, void* stream) {
-  if (!adam_step_state || !next_cols || !num_embeddings || !dedup_tables || !next_dedup_ws)
-    return fail(TT_EINVAL, "tower_tail: null pointer");
-  if (id_dtype != TT_I32 && id_dtype != TT_I64) return fail(TT_EINVAL, "tower_tail: ids must be int32/int64");
-  if (dedup_max_lookups < 2 * B || dedup_max_lookups >= (int64_t)DD_CNT_MASK ||
-      dedup_ws_bytes < dedup_layout(nullptr, dedup_max_lookups, nullptr) ||
-      (reinterpret_cast<uintptr_t>(next_dedup_ws) & 63))
-    return fail(TT_ECAPACITY, "tower_tail: dedup workspace too small / misaligned");
+static int fused_wgrad_insert_adagrad(const tt_launch_plan_t& p, void* stream) {
+  if (!p.wgrad.adam_step_state) return fail(TT_EINVAL, "tower_tail: null pointer");
+  const int64_t B = p.B;
+  tt_adagrad_role_t g = p.adagrad;
+  g.B = B;  // the ring tail's lookups per feature are the plan's B (tt_launch: adagrad.B is 0 or B)
+  tt_insert_role_t in = p.insert;
+  in.dedup_ws_bytes = g.dedup_ws_bytes, in.dedup_max_lookups = g.dedup_max_lookups;  // one size: the ADAGRAD role's
+  InsertArgs ins{};
+  int rc = insert_args(in, B, "tower_tail", ins);
+  if (rc) return rc;
   WgradArgs a2{};
   int64_t wgs = 0;
-  int rc = wgrad_args(shape, B, loss, workspace, ws_bytes, a2, &wgs);
-  if (rc) return rc;
   TowerLayout L;
-  tower_layout(shape, B, &L);
-  char* ws = reinterpret_cast<char*>(workspace);
-  a2.step_state = adam_step_state;
-  a2.adam_pre = reinterpret_cast<float*>(ws + L.o_counter);
-  a2.lr = adam_lr;
-  a2.beta1 = adam_beta1;
-  a2.beta2 = adam_beta2;
-  InsertArgs ins{};
-  rc = insert_args(B, next_cols, id_dtype, num_embeddings, dedup_tables, next_dedup_ws, dedup_max_lookups, ins);
-  if (rc) return rc;
+  if ((rc = wgrad_args(p.shape, B, p.workspace, p.ws_bytes, p.wgrad, a2, &wgs, L))) return rc;
+  char* ws = reinterpret_cast<char*>(p.workspace);
   DdUpdateArgs d{};
   int64_t dd_grid = 0;
-  rc = dedup_update_args(tables, T, features, F, B, grad, ldg, weights, state, lr, emb_eps, dedup_ws, dedup_ws_bytes,
-                         dedup_max_lookups, d, &dd_grid);
-  if (rc) return rc;
+  if ((rc = dedup_update_args(g, d, &dd_grid))) return rc;
   d.skip_single = 1;
   bool list = L.rows && L.lds;  // the row-owned T1 listed the multi-lookup rows and freed the single slots
 #if TT_EXPERIMENTS
@@ -3832,7 +3708,7 @@ static int fused_wgrad_insert_adagrad(const tt_tower_shape_t* shape, int64_t B, 
   // the list role (the ring) in a kernel of its own code: no slot-role instructions in its footprint
   auto kern = list ? tower_tail_kernel<true> : tower_tail_kernel<false>;
   kern<<<dim3((unsigned)(n_ins + wgs + dd_grid)), dim3(256), 0, as_stream(stream)>>>(
-      a2, reinterpret_cast<const WgradTile*>(ws + a2.tiles_off), ins, d, (int)n_ins, (int)wgs, stamps);
+      a2, wgrad_tiles(p.workspace, a2), ins, d, (int)n_ins, (int)wgs, stamps);
   return check_launch("tower_wgrad_pre_insert_rowwise_adagrad");
 }
 
@@ -3861,14 +3737,15 @@ int tt_tower_fwd_bwd_indexed_multi_bf16(const tt_tower_shape_t* shape, int64_t B
   a.ifeat0[0] = 0;
   a.ifeat0[1] = shape->in_dim[0] / D;
   a.iD = D;
-  return launch_t1(shape, B, a, nullptr, shape->in_dim[0] + shape->in_dim[1], nullptr, params, labels, label_dtype,
-                   grad_scale, logits, workspace, ws_bytes, stream);
+  return launch_t1(shape, B, a, nullptr, shape->in_dim[0] + shape->in_dim[1], nullptr,
+                   {params, labels, label_dtype, grad_scale, logits, workspace, ws_bytes, stream});
 }
 
-static int tower_indexed2(const tt_tower_shape_t* shape, int64_t B, const int32_t* const* pos_in,
-                          const int32_t* const* pos_out, const void* const* rows_in, float* const* grad_rows_out,
-                          const float* params, const void* labels, int label_dtype, float grad_scale, float* logits,
-                          void* workspace, size_t ws_bytes, const tt_peer_direct_t* direct, void* stream) {
+int tt_tower_fwd_bwd_indexed2_bf16(const tt_tower_shape_t* shape, int64_t B, const int32_t* const* pos_in,
+                                   const int32_t* const* pos_out, const void* const* rows_in,
+                                   float* const* grad_rows_out, const float* params, const void* labels,
+                                   int label_dtype, float grad_scale, float* logits, void* workspace, size_t ws_bytes,
+                                   const tt_peer_direct_t* direct, void* stream) {
   if (!pos_in || !pos_out || !rows_in || !grad_rows_out) return fail(TT_EINVAL, "tower_indexed2: null pointer");
   TowerArgs a{};
   if (direct) {
@@ -3888,29 +3765,16 @@ static int tower_indexed2(const tt_tower_shape_t* shape, int64_t B, const int32_
     a.gdst[t] = grad_rows_out[t];
   }
   return launch_t1(shape, B, a, nullptr,
-                   std::max(shape->in_col[0] + shape->in_dim[0], shape->in_col[1] + shape->in_dim[1]), nullptr, params,
-                   labels, label_dtype, grad_scale, logits, workspace, ws_bytes, stream);
-}
-
-int tt_tower_fwd_bwd_indexed2_bf16(const tt_tower_shape_t* shape, int64_t B, const int32_t* const* pos_in,
-                                   const int32_t* const* pos_out, const void* const* rows_in,
-                                   float* const* grad_rows_out, const float* params, const void* labels,
-                                   int label_dtype, float grad_scale, float* logits, void* workspace, size_t ws_bytes,
-                                   const tt_peer_direct_t* direct, void* stream) {
-  return tower_indexed2(shape, B, pos_in, pos_out, rows_in, grad_rows_out, params, labels, label_dtype, grad_scale,
-                        logits, workspace, ws_bytes, direct, stream);
+                   std::max(shape->in_col[0] + shape->in_dim[0], shape->in_col[1] + shape->in_dim[1]), nullptr,
+                   {params, labels, label_dtype, grad_scale, logits, workspace, ws_bytes, stream});
 }
 
 // ---- launch plans (include/tt_mi355x.h): the multi-role fused launches behind one entry point ----
 int tt_launch(const tt_launch_plan_t* p, void* stream) {
   if (!p) return fail(TT_EINVAL, "launch: null plan");
-  const tt_wgrad_role_t& w = p->wgrad;
   const tt_update_role_t& u = p->update;
   const tt_insert_role_t& in = p->insert;
   const tt_adagrad_role_t& g = p->adagrad;
-  const tt_route_role_t& r = p->route;
-  const tt_gather_role_t& ga = p->gather;
-  const int64_t B = p->B;
   auto need_multi = [&](int want) {
     return g.multi_only == want ? TT_OK
                                 : fail(TT_EINVAL, want ? "launch: this plan updates only rows looked up more than once "
@@ -3930,61 +3794,32 @@ int tt_launch(const tt_launch_plan_t* p, void* stream) {
       if ((rc = need_multi(1))) return rc;
       // the ring tail's lookups per feature are the plan's B (the tower batch): a different
       // adagrad.B is a caller error, not something to ignore
-      if (g.B && g.B != B) return fail(TT_EINVAL, "launch: this plan's ADAGRAD role uses the plan's B (adagrad.B = 0 or B)");
+      if (g.B && g.B != p->B) return fail(TT_EINVAL, "launch: this plan's ADAGRAD role uses the plan's B (adagrad.B = 0 or B)");
       if ((in.dedup_ws_bytes && in.dedup_ws_bytes != g.dedup_ws_bytes) ||
           (in.dedup_max_lookups && in.dedup_max_lookups != g.dedup_max_lookups))
         return fail(TT_EINVAL, "launch: the ring's two dedup workspaces have one size (the ADAGRAD role's)");
-      return fused_wgrad_insert_adagrad(p->shape, B, w.loss, p->workspace, p->ws_bytes, w.adam_step_state, w.adam_lr,
-                                        w.adam_beta1, w.adam_beta2, in.next_cols, in.id_dtype, in.num_embeddings,
-                                        in.dedup_tables, g.tables, g.T, g.features, g.F, g.grad, g.ldg, g.weights,
-                                        g.state, g.lr, g.eps, g.dedup_ws, in.next_dedup_ws, g.dedup_ws_bytes,
-                                        g.dedup_max_lookups, stream);
+      return fused_wgrad_insert_adagrad(*p, stream);
     case TT_ROLE_WGRAD | TT_ROLE_INSERT:
-      return fused_wgrad_insert(p->shape, B, w.loss, p->workspace, p->ws_bytes, w.adam_step_state, w.adam_lr,
-                                w.adam_beta1, w.adam_beta2, in.next_cols, in.id_dtype, in.num_embeddings,
-                                in.dedup_tables, in.next_dedup_ws, in.dedup_ws_bytes, in.dedup_max_lookups, stream);
+      return fused_wgrad_insert(*p, stream);
     case TT_ROLE_UPDATE | TT_ROLE_ADAGRAD | TT_ROLE_RESOLVE:
       if ((rc = need_multi(1)) || (rc = adam_mode())) return rc;
-      return fused_update_adagrad_resolve(p->shape, B, u.params, u.exp_avg, u.exp_avg_sq, u.eps, u.beta1, u.beta2,
-                                          u.weight_decay, u.grads_out, p->workspace, p->ws_bytes, g.tables, g.T,
-                                          g.features, g.F, g.B, g.grad, g.ldg, g.weights, g.state, g.lr, g.eps,
-                                          g.dedup_ws, p->resolve.dedup_ws, g.dedup_ws_bytes, g.dedup_max_lookups,
-                                          stream);
+      return fused_update_adagrad_resolve(*p, stream);
     case TT_ROLE_WGRAD | TT_ROLE_ADAGRAD:
       if ((rc = need_multi(0))) return rc;
-      return fused_wgrad_adagrad(p->shape, B, w.loss, p->workspace, p->ws_bytes, g.tables, g.T, g.features, g.F, g.B,
-                                 g.grad, g.ldg, g.weights, g.state, g.lr, g.eps, g.dedup_ws, g.dedup_ws_bytes,
-                                 g.dedup_max_lookups, w.adam_step_state, w.adam_lr, w.adam_beta1, w.adam_beta2,
-                                 stream);
+      return fused_wgrad_adagrad(*p, stream);
     case TT_ROLE_UPDATE | TT_ROLE_ADAGRAD:
       if ((rc = need_multi(0)) || (rc = adam_mode())) return rc;
-      return fused_update_adagrad(p->shape, B, u.params, u.exp_avg, u.exp_avg_sq, u.eps, u.beta1, u.beta2,
-                                  u.weight_decay, u.grads_out, p->workspace, p->ws_bytes, g.tables, g.T, g.features,
-                                  g.F, g.B, g.grad, g.ldg, g.weights, g.state, g.lr, g.eps, g.dedup_ws,
-                                  g.dedup_ws_bytes, g.dedup_max_lookups, stream);
+      return fused_update_adagrad(*p, stream);
     case TT_ROLE_WGRAD | TT_ROLE_ROUTE_COUNT | TT_ROLE_ADAGRAD:
       if ((rc = need_multi(0))) return rc;
-      return fused_wgrad_route_count_adagrad(p->shape, B, w.loss, p->workspace, p->ws_bytes, w.adam_step_state,
-                                             w.adam_lr, w.adam_beta1, w.adam_beta2, r.F, r.cols, r.id_dtype,
-                                             r.num_embeddings, r.block_sizes, r.owners, r.W, r.segs, r.send, r.pos_in,
-                                             r.pos_out, r.overflow, r.route_ws, r.route_ws_bytes, g.tables, g.T,
-                                             g.features, g.F, g.B, g.grad, g.ldg, g.weights, g.state, g.lr, g.eps,
-                                             g.dedup_ws, g.dedup_ws_bytes, g.dedup_max_lookups, p->wait, stream);
+      return fused_wgrad_route_count_adagrad(*p, stream);
     case TT_ROLE_ROUTE_COUNT | TT_ROLE_ADAGRAD:
       if ((rc = need_multi(0))) return rc;
-      return fused_route_count_adagrad(r.F, B, r.cols, r.id_dtype, r.num_embeddings, r.block_sizes, r.owners, r.W,
-                                       r.segs, r.send, r.pos_in, r.pos_out, r.overflow, r.route_ws, r.route_ws_bytes,
-                                       g.tables, g.T, g.features, g.F, g.B, g.grad, g.ldg, g.weights, g.state, g.lr,
-                                       g.eps, g.dedup_ws, g.dedup_ws_bytes, g.dedup_max_lookups, p->wait, stream);
+      return fused_route_count_adagrad(*p, stream);
     case TT_ROLE_UPDATE | TT_ROLE_ROUTE_PLACE | TT_ROLE_GATHER:
       if (!u.replicated) return fail(TT_EINVAL, "launch: launch G's UPDATE role writes the replicated gradient "
                                                 "(update.replicated = 1)");
-      return fused_grads_route_place_gather(p->shape, B, u.params, u.base, u.copies, u.offsets, u.scale, p->workspace,
-                                            p->ws_bytes, r.F, r.cols, r.id_dtype, r.num_embeddings, r.block_sizes,
-                                            r.owners, r.W, r.segs, r.send, r.pos_in, r.pos_out, r.overflow, r.route_ws,
-                                            r.route_ws_bytes, ga.weights, ga.tables, ga.T, ga.recv, ga.block_i64,
-                                            ga.counts_i64, ga.seg_off, ga.slots, ga.rows_out, ga.out_stride, ga.bad,
-                                            ga.dedup_ws, ga.dedup_ws_bytes, ga.dedup_max_lookups, ga.direct, stream);
+      return fused_grads_route_place_gather(*p, stream);
     default:
       return fail(TT_EINVAL, "launch: no fused launch runs this set of roles (see tt_launch_plan_t)");
   }
