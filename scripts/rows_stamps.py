@@ -3,13 +3,18 @@ library) inside the production ring at the north-star shape: for each point, the
 workgroups of each wave's stamp (us from the workgroup's first wave start). Points: 0 start, 1 loads
 issued, 2 loads landed, 3 past barrier 1, 4 layer 0, 5 layer 1 (+ exchange write), 6 X / h strips,
 7 past barrier 2, 8 logit + dZ1, 9 dZ0, 10 dX, 11 row update / dX stores, 12 dZ strips, 13 bias sums,
-14 past barrier 3, 15 end."""
+14 past barrier 3, 15 end. The image wave (wave 4) stamps its own points in slot 8: 0 start, 1 image
+DMAs issued, 2 image landed, 3 past barrier 1. TT_EXPERIMENT_LIB may name an earlier experiment build
+under lib_var/; such a library may have no image wave and then never writes slot 8 (whatever the
+workspace held stays there), so the image wave's points are printed for this tree's experiment
+build only, or where IMAGE_WAVE=1 / 0 says so."""
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ["TT_T1_DEBUG"] = str(8 | int(os.environ.get("T1_ABLATE", "0")))  # + ablation bits (16: no image, 32: no rows)
-os.environ["TT_EXPERIMENT_LIB"] = "1"
+os.environ.setdefault("TT_EXPERIMENT_LIB", "1")
+image_wave = os.environ.get("IMAGE_WAVE", "1" if os.environ["TT_EXPERIMENT_LIB"] == "1" else "0") == "1"
 import torch  # noqa: E402
 
 from two_tower_recommender_model_amd.fused import FusedTwoTowerStep  # noqa: E402
@@ -35,6 +40,7 @@ for it in range(4):
         continue
     w = st.towers.ws[off:off + dbg_bytes].view(torch.int64)[8192:8192 + nwg * 16 * 9].view(nwg, 16, 9).cpu().double()
     extra = w[:, :4, 4:8]
+    img = w[:, :4, 8]
     w = w[:, :, :4]
     t0 = w[:, 0, :].min(dim=1, keepdim=True).values
     rel = (w - t0.unsqueeze(1)) / 100.0
@@ -46,6 +52,10 @@ for it in range(4):
     ex = (extra - t0.unsqueeze(1)) / 100.0
     for k, what in enumerate(["G^2 sums", "step + LDS write-back", "row stores issued", "state / dX stores"]):
         print(f"  u{k} {what:24s}" + " ".join(f"{float(x):8.2f}" for x in ex[:, k, :].median(dim=0).values))
+    if image_wave:
+        im = (img - t0) / 100.0
+        for k, what in enumerate(["start", "image DMAs issued", "image landed", "past barrier 1"]):
+            print(f"  i{k} image wave: {what:20s}{float(im[:, k].median()):8.2f}")
     tmin = w[:, 0, :].min()
     print("launch span (us from the first workgroup's start): last start %.2f, end p50 %.2f, last end %.2f" % (
         float((w[:, 0, :].max() - tmin) / 100), float(((w[:, 15, :].max(dim=1).values - tmin) / 100).median()),

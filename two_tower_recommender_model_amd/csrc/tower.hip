@@ -1221,8 +1221,9 @@ __global__ void __launch_bounds__(T1_THREADS) tower_l2_kernel(TowerArgs a) {
 
 // ---------------------------------------------------------------------------------------------
 // T1, row-owned form (tower_rows_kernel): the production shape — both towers over 128-wide
-// single-hot rows gathered from the tables, layers [128, 64]. One workgroup of 4 waves per 32
-// batch rows; wave w runs tower t = w >> 1 over rows 16 (w & 1) .. + 15 of the tile through the
+// single-hot rows gathered from the tables, layers [128, 64]. One workgroup of 4 compute waves (and
+// the image wave, which fills the LDS weight image while the ids and rows come in) per 32
+// batch rows; wave w < 4 runs tower t = w >> 1 over rows 16 (w & 1) .. + 15 of the tile through the
 // whole chain (gather, both layers, logit, dZ1, dZ0, dX, the in-place row-wise Adagrad) with every
 // activation in registers: three barriers (the weight image landed; the towers' outputs exchanged
 // for the logit; the workgroup's bias / loss partials combined), no LDS round trip between layers.
@@ -1243,6 +1244,9 @@ __global__ void __launch_bounds__(T1_THREADS) tower_l2_kernel(TowerArgs a) {
 constexpr int RK_IN = 128, RK_W0 = 128, RK_W1 = 64;
 constexpr int RK_IMG_T = (RK_W0 + RK_W1) * 256;  // bytes per tower: W0 [128][128], then W1 [64][128]
 constexpr int RK_IMG = 2 * RK_IMG_T;             // 98,304 B
+// four compute waves (threads 0 .. 255: everything indexed by threadIdx.x is theirs) and the image
+// wave (wave 4), which only copies the image into LDS and keeps the barrier count
+constexpr int RK_THREADS = 320;
 // 16-B chunk swizzle of image row `row` (256-B rows): b128 reads of 16 permuted rows x one chunk
 // and transposed reads of 8 rows x 4 chunks (two 16-lane groups) hit distinct banks
 __host__ __device__ __forceinline__ int rk_swz(int row) {
@@ -1416,9 +1420,13 @@ __device__ __forceinline__ float rk_label(RkRaw r, int dt) {
 // extra points in wave slots 4 .. 7
 #define RK_STAMP2(k) \
   do { if (a.stamps && lane == 0) a.stamps[8192 + ((int64_t)blockIdx.x * 16 + (k)) * 9 + 4 + wid] = (int64_t)__builtin_amdgcn_s_memrealtime(); } while (0)
+// the image wave's points (0 start, 1 DMAs issued, 2 landed, 3 past barrier 1) in wave slot 8
+#define RK_STAMP_IMG(k) \
+  do { if (a.stamps && lane == 0) a.stamps[8192 + ((int64_t)blockIdx.x * 16 + (k)) * 9 + 8] = (int64_t)__builtin_amdgcn_s_memrealtime(); } while (0)
 #else
 #define RK_STAMP(k) do { } while (0)
 #define RK_STAMP2(k) do { } while (0)
+#define RK_STAMP_IMG(k) do { } while (0)
 #endif
 // ---------------------------------------------------------------------------------------------
 // T3: reduce + Adam + bf16 weight copies
@@ -1554,6 +1562,29 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   __shared__ __attribute__((aligned(16))) float xr[4][16 * IN];     // per wave: its 16 gathered rows
                                                                     // (fp32, 16-B chunk c of row n at c ^ n)
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  typedef __attribute__((address_space(3))) void lds_void;
+  typedef __attribute__((address_space(1))) void glb_void;
+  // ---- the image wave (wave 4 of RK_THREADS): the whole weight image -> LDS by LDS-DMA, 1 KB per
+  // wave instruction (the global image is in the LDS layout, rk_off: a straight copy). The image
+  // does not depend on the ids, and vmcnt is per wave: the compute waves' id / row waits never
+  // count these DMAs, and nothing of the image passes through their registers. The wave then only
+  // keeps the workgroup's barrier count (three, as every path of the compute waves)
+  if (wid == 4) {
+    RK_STAMP_IMG(0);
+    if (!TDBG(16)) {  // EXPERIMENT (timing only): no image fill
+#pragma unroll
+      for (int k = 0; k < RK_IMG / 1024; ++k)
+        __builtin_amdgcn_global_load_lds((glb_void*)(a.wimg + k * 1024 + lane * 16), (lds_void*)(wimg + k * 1024), 16, 0, 0);
+    }
+    RK_STAMP_IMG(1);
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the image landed
+    RK_STAMP_IMG(2);
+    __syncthreads();  // barrier 1: the image landed
+    RK_STAMP_IMG(3);
+    __syncthreads();  // barrier 2: the towers' outputs exchanged
+    __syncthreads();  // barrier 3: the bias / loss partials combined
+    return;
+  }
   const int t = wid >> 1, h = wid & 1, q = lane >> 4, n = lane & 15;
   // the tile: XCD x runs tiles [x n / 8, (x + 1) n / 8) (xcd_remap), so the 256-row slices the
   // tail's T2 tiles read (also placed a contiguous 1/8 per XCD) were written through that XCD's L2
@@ -1563,7 +1594,7 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   RK_STAMP(0);
   // ---- 0. loads in dependency order (vmcnt retires in issue order: a wait for a load also waits
   // for everything issued before it): the ids, the label, the biases (raw: no conversion between
-  // them); the weight image -> LDS (LDS-DMA, 1 KB per wave instruction); the row
+  // them); the row (the weight image is the image wave's, above)
   const bool wide = a.gid_dtype == TT_I64;
   const int64_t mc = live ? m : 0;  // dead rows of a ragged tile read row 0 of every column
   RkRaw id_raw{0u, 0u}, pout_raw{0u, 0u};
@@ -1588,19 +1619,9 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) b1v[mt] = *reinterpret_cast<const f32x4*>(b1p + 32 * (mt >> 1) + 8 * q + 4 * (mt & 1));
   };
-  // the weight image (no dependency): 24 16-B loads per lane into registers, issued while the ids
-  // come back (plain loads: with an LDS-DMA in flight the compiler waits vmcnt(0) at the first use
-  // of any load, so the ids must land before the first DMA is issued), written to LDS below
-  bf16x8 wreg[RK_IMG / 1024 / 4];
-  auto load_image = [&]() {
-#pragma unroll
-    for (int k = 0; k < RK_IMG / 1024 / 4; ++k)
-      wreg[k] = TDBG(16) ? (bf16x8)(__bf16)0.f  // EXPERIMENT (timing only): no image fill
-                         : *reinterpret_cast<const bf16x8*>(a.wimg + (wid + 4 * k) * 1024 + lane * 16);
-  };
+  // (with an LDS-DMA in flight the compiler waits vmcnt(0) at the first use of any load, so in
+  // these waves the ids must land before the first row DMA is issued: no DMA of the image here)
   load_biases();
-  __builtin_amdgcn_sched_barrier(0);
-  load_image();
   __builtin_amdgcn_sched_barrier(0);
   // direct exchange: this workgroup's first share of the copy region (exchange A's keys), loaded
   // now beside the prologue's loads, stored at the end (the rest of a large share there too)
@@ -1629,8 +1650,6 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   }
   const float* tab = POOL ? a.pooled + a.s.in_col[t] : (t ? a.gtab[1] : a.gtab[0]);
   const int64_t rstride = POOL ? a.ldp : IN;  // floats between consecutive source rows
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef __attribute__((address_space(1))) void glb_void;
   // the wave's 16 rows -> LDS by LDS-DMA, two whole 512-B rows per wave instruction (two TLB pages
   // per instruction, full lines; a lane-per-row-piece register gather touches 16 rows per
   // instruction): lane l of instruction i carries 16-B chunk (l & 31) ^ row of row 2 i + (l >> 5),
@@ -1674,12 +1693,9 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     dd_insert_begin(a.dd, key, li, pend);
   }
   RK_STAMP(1);
-  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the rows (LDS-DMA) and the image registers
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the rows (LDS-DMA) and the small loads
   RK_STAMP(2);
-#pragma unroll
-  for (int k = 0; k < RK_IMG / 1024 / 4; ++k)
-    *reinterpret_cast<bf16x8*>(wimg + (wid + 4 * k) * 1024 + lane * 16) = wreg[k];
-  __syncthreads();
+  __syncthreads();  // barrier 1: the image wave's DMAs landed before it arrived
   RK_STAMP(3);
   // this lane's row in the B layout: xv[mt] = features 32 (mt >> 1) + 8 q + 4 (mt & 1) .. + 3 (fp32)
   f32x4 xv[8];
@@ -1968,7 +1984,7 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   RK_STAMP(15);
 }
 template <bool UPD, bool IDX = false, int IN = 128, bool POOL = false>
-__global__ void __launch_bounds__(256) tower_rows_kernel(TowerArgs a) {
+__global__ void __launch_bounds__(RK_THREADS) tower_rows_kernel(TowerArgs a) {
   tower_rows_body<UPD, IDX, IN, POOL>(a);
 }
 
@@ -3081,14 +3097,14 @@ static int launch_t1(const tt_tower_shape_t* shape, int64_t B, TowerArgs& a, con
   if (rows_t1) {
     a.wimg = ws + L.o_wimg;
     if (a.gpos[0])
-      i0 == 64 ? tower_rows_kernel<false, true, 64><<<g, dim3(256), 0, as_stream(stream)>>>(a)
-               : tower_rows_kernel<false, true, 128><<<g, dim3(256), 0, as_stream(stream)>>>(a);
+      i0 == 64 ? tower_rows_kernel<false, true, 64><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a)
+               : tower_rows_kernel<false, true, 128><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a);
     else if (a.uw[0])
-      i0 == 64 ? tower_rows_kernel<true, false, 64><<<g, dim3(256), 0, as_stream(stream)>>>(a)
-               : tower_rows_kernel<true, false, 128><<<g, dim3(256), 0, as_stream(stream)>>>(a);
+      i0 == 64 ? tower_rows_kernel<true, false, 64><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a)
+               : tower_rows_kernel<true, false, 128><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a);
     else
-      i0 == 64 ? tower_rows_kernel<false, false, 64><<<g, dim3(256), 0, as_stream(stream)>>>(a)
-               : tower_rows_kernel<false, false, 128><<<g, dim3(256), 0, as_stream(stream)>>>(a);
+      i0 == 64 ? tower_rows_kernel<false, false, 64><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a)
+               : tower_rows_kernel<false, false, 128><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a);
     return check_launch(a.uw[0] ? "tower_rows_gather_update" : "tower_rows_gather");
   }
 #if TT_EXPERIMENTS
@@ -3096,8 +3112,8 @@ static int launch_t1(const tt_tower_shape_t* shape, int64_t B, TowerArgs& a, con
 #endif
   if (rows_pool && rows_pool_ok) {
     a.wimg = ws + L.o_wimg;
-    i0 == 64 ? tower_rows_kernel<false, false, 64, true><<<g, dim3(256), 0, as_stream(stream)>>>(a)
-             : tower_rows_kernel<false, false, 128, true><<<g, dim3(256), 0, as_stream(stream)>>>(a);
+    i0 == 64 ? tower_rows_kernel<false, false, 64, true><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a)
+             : tower_rows_kernel<false, false, 128, true><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a);
     return check_launch("tower_rows_pooled");
   }
   if (a.uw[0]) {  // in-place update of single-lookup rows: compile-time shapes only
