@@ -646,6 +646,49 @@ int tt_topk_mips_filtered(const void* queries, int q_dtype, int64_t ldq, const v
                           const uint32_t* allow, const int32_t* excl_values, const int64_t* excl_offsets,
                           int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream);
 
+/* IVF (inverted-file) approximate top-k (ABI 4 addition): the fine step of the approximate vector
+ * index that 04_evaluate_retrieval.py:112-153 queries. The index holds the N item rows grouped into
+ * L lists (a k-means partition; the coarse step, "the nprobe nearest centroids of a query", is
+ * tt_topk_mips with the centroids as items):
+ *   rows [P, E] bf16, contiguous, 16-byte aligned: the item rows in list order, rounded to
+ *     nearest-even once (the rounding tt_topk_mips applies on load), padding rows between lists;
+ *   bias [P] fp32 or NULL, labels [P] int32 (the row's original item index; -1 on padding), in the
+ *     same order; within a list the labels ascend;
+ *   list_begin [L] int64, list_len [L] int32: list l is rows [list_begin[l], list_begin[l] + list_len[l]);
+ *     lists do not overlap and every item is in exactly one.
+ * queries [M, E] fp32 or bf16 with row stride ldq; probes [M, nprobe] int32: the lists query m scans,
+ * distinct within a row; a value outside [0, L) (-1 by convention) is no probe. excl_values /
+ * excl_offsets: both NULL or as tt_topk_mips_filtered (original item indices, ascending per query).
+ * CONTRACT: ids / scores [M, k] are exactly what tt_topk_mips_filtered returns for the same queries,
+ * the N original rows and their bias when query m is denied every item outside its probed lists (and
+ * its exclusion segment): the same score bits for the same pairs (the MFMA chain over E, + bias), the
+ * same order (higher score, then lower ORIGINAL index), ids are original item indices, tail id -1 /
+ * score -inf where fewer than k remain. Hence bit-identical across runs, and independent of the
+ * order of a query's probes and of the order in which the grouping places the pairs.
+ * Device data the host cannot validate never causes an out-of-range access: a list with
+ * list_len < 0 or list_begin + list_len > P (or list_begin < 0) is treated as empty.
+ * Everything runs on `stream` (a memset and five kernels: count, scan over L, scatter, list scan,
+ * merge), no allocation, no synchronisation; the workspace (tt_ivf_scan_workspace_bytes: M * nprobe
+ * partial lists of k keys, and the grouping tables) need not be initialised.
+ * Limits (TT_EINVAL otherwise, before any launch): E a multiple of 32 in [32, 128]; 1 <= k <=
+ * TT_TOPK_MAX_K; 1 <= nprobe <= 64; 1 <= L <= 2^20; M >= 1, M * nprobe < 2^31; 1 <= P < 2^31; no
+ * NULL pointer except bias and the exclusion pair. tt_ivf_scan_workspace_bytes returns 0 outside them. */
+size_t tt_ivf_scan_workspace_bytes(int64_t M, int nprobe, int k, int64_t L);
+int tt_ivf_scan(const void* queries, int q_dtype, int64_t ldq, int64_t M, int E, const void* rows, const float* bias,
+                const int32_t* labels, int64_t P, const int64_t* list_begin, const int32_t* list_len, int64_t L,
+                const int32_t* probes, int nprobe, const int32_t* excl_values, const int64_t* excl_offsets, int k,
+                int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream);
+
+/* The centroid update of the index's k-means (ABI 4 addition): out[l, :] = the mean of
+ * rows[order[i], :] over i in [seg_offsets[l], seg_offsets[l + 1]) for each of L segments; rows
+ * [n, E] fp32 or bf16 with row stride ld, order [n] int64 (row indices; one outside [0, n) adds
+ * nothing), seg_offsets [L + 1] int64 non-decreasing (clamped to [0, n]), out [L, E] fp32. Every
+ * element is summed in fp32 in one fixed order (no atomics), so the result is bit-identical from run
+ * to run; an empty segment leaves its out row untouched. Limits: 1 <= E <= 4096, ld >= E, n >= 1,
+ * 1 <= L <= 2^20, no NULL pointer. */
+int tt_ivf_segment_mean(const void* rows, int dtype, int64_t ld, int64_t n, int E, const int64_t* order,
+                        const int64_t* seg_offsets, int64_t L, float* out, void* stream);
+
 /* SETUP ONLY (allocating, synchronising): device memory for embedding tables on the current
  * device, physically contiguous when the driver can give it (hipDeviceMallocContiguous: the largest
  * page fragments for the random row gathers; *contiguous = 1), plain device memory otherwise

@@ -330,6 +330,10 @@ SIGNATURES = {
     "tt_topk_mips": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "tt_topk_mips_filtered": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _sz, _vp]),
+    "tt_ivf_scan_workspace_bytes": (_sz, [_i64, _int, _int, _i64]),
+    "tt_ivf_scan": (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp, _vp, _int,
+                           _vp, _vp, _vp, _sz, _vp]),
+    "tt_ivf_segment_mean": (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp]),
     "tt_table_alloc": (_int, [_sz, _pvp, C.POINTER(C.c_int)]),
     "tt_table_free": (_int, [_vp]),
 }
@@ -391,6 +395,9 @@ COMPUTE_ENTRY_POINTS = [
     "tt_topk_mips",
     "tt_topk_mips_filtered",
 ]
+# later ABI 4 additions (csrc/ivf.hip): bound through SIGNATURES like the rest, not part of the
+# count above, which tt_num_entry_points() pins at the entry points up to tt_topk_mips_filtered
+IVF_ENTRY_POINTS = ["tt_ivf_scan", "tt_ivf_segment_mean"]
 
 _lib = None
 _lock = threading.Lock()

@@ -21,12 +21,15 @@
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, List, Optional, Sequence, Tuple
+from typing import TYPE_CHECKING, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
 from .metrics import AUROC
+
+if TYPE_CHECKING:
+    from .ivf import IVFIndex
 
 DEFAULT_FEATURES = ("user_id", "product_id")  # cat_cols of 03_model_training.py:39
 
@@ -194,8 +197,8 @@ def _retrieval_filters(N: int, M: int, device, allow, seen_values, seen_offsets)
 
 def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metric: str = "dot",
              query_chunk: int = 1 << 16, bias: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
-             seen_values: Optional[torch.Tensor] = None,
-             seen_offsets: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             seen_values: Optional[torch.Tensor] = None, seen_offsets: Optional[torch.Tensor] = None,
+             index: Optional["IVFIndex"] = None, nprobe: int = 32) -> Tuple[torch.Tensor, torch.Tensor]:
     """The query loop of 04_evaluate_retrieval.py:131-153 without an index: for each row of
     ``user_emb`` the exact top ``k`` rows of ``item_emb`` (ops.topk_mips), ``query_chunk`` queries per
     launch. ``metric``: "dot" (the model's own score) or "l2" (the order of the reference's vector
@@ -208,9 +211,22 @@ def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metri
     ``filters=`` of 04_evaluate_retrieval.py:100); ``seen_values`` / ``seen_offsets`` [M + 1] are each
     user's already-seen items (jagged, in the reference's labels as ``target_values``; labels outside
     1..N are dropped), never returned to that user. The lists are sorted once; a chunk of queries
-    takes a view of the offsets."""
+    takes a view of the offsets.
+
+    ``index`` (ivf.IVFIndex over the same ``item_emb``, built for the same ``metric``): the
+    approximate query instead, each user against its ``nprobe`` nearest lists only
+    (IVFIndex.search); ids, scores and the seen lists as above, ``item_emb`` and ``bias`` are not
+    read (the index holds its own copy), ``allow`` is not supported."""
     if metric not in ("dot", "l2"):
         raise ValueError("metric must be 'dot' or 'l2'")
+    if index is not None:
+        if allow is not None:
+            raise ValueError("allow masks are not supported with an index")
+        if index.metric != metric:
+            raise ValueError(f"the index was built for metric {index.metric!r}, not {metric!r}")
+        _, seen = _retrieval_filters(index.N, user_emb.shape[0], user_emb.device, None, seen_values, seen_offsets)
+        i, s = index.search(user_emb, k, nprobe, seen=seen, query_chunk=query_chunk)
+        return i + 1, s
     if metric == "l2" and bias is None:
         bias = l2_bias(item_emb)
     if metric == "dot":
@@ -231,34 +247,39 @@ def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metri
 def retrieve_fused(step, user_rows: torch.Tensor, k: int = 100, metric: str = "dot",
                    item_emb: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
                    seen_values: Optional[torch.Tensor] = None, seen_offsets: Optional[torch.Tensor] = None,
-                   query_chunk: int = 1 << 16) -> Tuple[torch.Tensor, torch.Tensor]:
+                   query_chunk: int = 1 << 16, index: Optional["IVFIndex"] = None,
+                   nprobe: int = 32) -> Tuple[torch.Tensor, torch.Tensor]:
     """retrieve() for a FusedTwoTowerStep: rows ``user_rows`` (int64 row indices) of the user table
     through the query tower (as export does), against the item table through the candidate tower
     (export_fused, unless its embeddings ``item_emb`` are passed in). ``allow``, ``seen_values`` /
-    ``seen_offsets`` and ``query_chunk`` as retrieve()."""
+    ``seen_offsets``, ``query_chunk``, ``index`` and ``nprobe`` as retrieve() (with an index the
+    item tower is not run)."""
     towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
     x = step.tables.table_view(0)[user_rows.to(step.device)]
     for w, b in towers[0]:
         x = ops.linear_fwd([x], [w.contiguous()], [b], relu=True)[0]
-    if item_emb is None:
+    if item_emb is None and index is None:
         item_emb = export_fused(step, "candidate")[1]
     return retrieve(x, item_emb, k=k, metric=metric, query_chunk=query_chunk, allow=allow, seen_values=seen_values,
-                    seen_offsets=seen_offsets)
+                    seen_offsets=seen_offsets, index=index, nprobe=nprobe)
 
 
 def evaluate_retrieval(step, user_rows: torch.Tensor, target_values: torch.Tensor, target_offsets: torch.Tensor,
                        k: int = 100, metric: str = "dot", item_emb: Optional[torch.Tensor] = None,
                        allow: Optional[torch.Tensor] = None, seen_values: Optional[torch.Tensor] = None,
-                       seen_offsets: Optional[torch.Tensor] = None, query_chunk: int = 1 << 16) -> Dict[str, object]:
+                       seen_offsets: Optional[torch.Tensor] = None, query_chunk: int = 1 << 16,
+                       index: Optional["IVFIndex"] = None, nprobe: int = 32) -> Dict[str, object]:
     """Retrieval evaluation of 04_evaluate_retrieval.py:202-226 (mlflow.evaluate, model_type
     "retriever"): the top ``k`` item ids of every user row against its jagged ground truth
     (``target_values`` item ids in the reference's labels, ``target_offsets`` [M + 1]);
     metrics.retrieval_metrics' dict. ``allow`` and ``seen_values`` / ``seen_offsets`` as retrieve():
     with each user's training positives as the seen set, the held-out items are ranked among the
-    items the user has not seen, which is the usual protocol."""
+    items the user has not seen, which is the usual protocol. ``index`` / ``nprobe`` as retrieve():
+    the approximate query (ivf.IVFIndex) in place of the exact one."""
     from .metrics import retrieval_metrics
 
     ids, _ = retrieve_fused(step, user_rows, k=k, metric=metric, item_emb=item_emb, allow=allow,
-                            seen_values=seen_values, seen_offsets=seen_offsets, query_chunk=query_chunk)
+                            seen_values=seen_values, seen_offsets=seen_offsets, query_chunk=query_chunk, index=index,
+                            nprobe=nprobe)
     ids = torch.where(ids > 0, ids, torch.full_like(ids, -1))  # padding (label 0) is no id
     return retrieval_metrics(ids, target_values.to(ids.device), target_offsets.to(ids.device), k)

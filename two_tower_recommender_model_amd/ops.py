@@ -962,3 +962,75 @@ def topk_mips(queries: torch.Tensor, items: torch.Tensor, k: int, bias: Optional
                                         ptr(ids), ptr(scores), ptr(ws), ws.numel(), stream_handle(dev)),
               "topk_mips_filtered")
     return ids, scores
+
+
+def ivf_scan(queries: torch.Tensor, rows: torch.Tensor, labels: torch.Tensor, list_begin: torch.Tensor,
+             list_len: torch.Tensor, probes: torch.Tensor, k: int, bias: Optional[torch.Tensor] = None,
+             exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The fine step of an IVF index (tt_ivf_scan): for each row of ``queries`` [M, E] the top ``k`` of
+    the items in the lists ``probes`` [M, nprobe] (int32, distinct within a row; a value outside
+    [0, L) is no probe) names. ``rows`` [P, E] bf16 are the item rows in list order, ``bias`` [P]
+    fp32 / ``labels`` [P] int32 (original item index) in the same order, list l = rows
+    [list_begin[l], list_begin[l] + list_len[l]) (int64 [L], int32 [L]). ``exclude`` as topk_mips,
+    in original item indices. Returns (ids [M, k] int64 original item indices, -1 where fewer than k
+    are left; scores [M, k] fp32): exactly topk_mips over the probed lists' items, bit for bit."""
+    _dev(queries, rows, labels, list_begin, list_len, probes, bias)
+    if exclude is not None:
+        _dev(*exclude)
+    if queries.dim() != 2 or rows.dim() != 2 or queries.shape[1] != rows.shape[1] or queries.stride(1) != 1:
+        raise _lib.TTError("ivf_scan: queries [M, E] (last dimension contiguous) and rows [P, E]")
+    if rows.dtype != torch.bfloat16 or not rows.is_contiguous():
+        raise _lib.TTError("ivf_scan: rows must be contiguous bf16 [P, E]")
+    M, E = queries.shape
+    P = rows.shape[0]
+    dev = queries.device
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != P or not bias.is_contiguous()):
+        raise _lib.TTError("ivf_scan: bias must be contiguous fp32 [P]")
+    if labels.dtype != torch.int32 or labels.numel() != P or not labels.is_contiguous():
+        raise _lib.TTError("ivf_scan: labels must be contiguous int32 [P]")
+    L = list_begin.numel()
+    if list_begin.dtype != torch.int64 or list_begin.dim() != 1 or not list_begin.is_contiguous() or \
+            list_len.dtype != torch.int32 or list_len.dim() != 1 or list_len.numel() != L or not list_len.is_contiguous():
+        raise _lib.TTError("ivf_scan: list_begin must be contiguous int64 [L] and list_len int32 [L]")
+    if probes.dtype != torch.int32 or probes.dim() != 2 or probes.shape[0] != M or not probes.is_contiguous():
+        raise _lib.TTError("ivf_scan: probes must be contiguous int32 [M, nprobe]")
+    nprobe = probes.shape[1]
+    xv = xo = None
+    if exclude is not None:
+        xv, xo = exclude
+        if xv.dtype != torch.int32 or xv.dim() != 1 or not xv.is_contiguous():
+            raise _lib.TTError("ivf_scan: exclude values must be contiguous int32 [L]")
+        if xo.dtype != torch.int64 or xo.dim() != 1 or xo.numel() != M + 1 or not xo.is_contiguous():
+            raise _lib.TTError("ivf_scan: exclude offsets must be contiguous int64 [M + 1]")
+        if xv.numel() == 0:  # no values: every segment is empty
+            xv = xo = None
+    lib = _lib_()
+    ids = torch.empty(M, k, dtype=torch.int64, device=dev)
+    scores = torch.empty(M, k, dtype=torch.float32, device=dev)
+    ws = scratch(lib.tt_ivf_scan_workspace_bytes(M, nprobe, k, L), dev, "ivf_scan")
+    check(lib.tt_ivf_scan(ptr(queries), _x_code(queries), queries.stride(0), M, E, ptr(rows), ptr(bias), ptr(labels), P,
+                          ptr(list_begin), ptr(list_len), L, ptr(probes), nprobe, ptr(xv), ptr(xo), k, ptr(ids),
+                          ptr(scores), ptr(ws), ws.numel(), stream_handle(dev)), "ivf_scan")
+    return ids, scores
+
+
+def ivf_segment_mean(rows: torch.Tensor, order: torch.Tensor, seg_offsets: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """out[l] = mean of rows[order[seg_offsets[l]:seg_offsets[l + 1]]] (tt_ivf_segment_mean): rows
+    [n, E] fp32 or bf16 (rows may be strided), order int64 [n], seg_offsets int64 [L + 1], out fp32
+    [L, E] updated in place (an empty segment's row stays). Summed in one fixed order: bit-identical
+    from run to run. Returns ``out``."""
+    _dev(rows, order, seg_offsets, out)
+    if rows.dim() != 2 or rows.stride(1) != 1:
+        raise _lib.TTError("ivf_segment_mean: rows [n, E], last dimension contiguous")
+    n, E = rows.shape
+    if order.dtype != torch.int64 or order.dim() != 1 or order.numel() != n or not order.is_contiguous():
+        raise _lib.TTError("ivf_segment_mean: order must be contiguous int64 [n]")
+    if seg_offsets.dtype != torch.int64 or seg_offsets.dim() != 1 or seg_offsets.numel() < 2 or \
+            not seg_offsets.is_contiguous():
+        raise _lib.TTError("ivf_segment_mean: seg_offsets must be contiguous int64 [L + 1]")
+    L = seg_offsets.numel() - 1
+    if out.dtype != torch.float32 or tuple(out.shape) != (L, E) or not out.is_contiguous():
+        raise _lib.TTError("ivf_segment_mean: out must be contiguous fp32 [L, E]")
+    check(_lib_().tt_ivf_segment_mean(ptr(rows), _x_code(rows), rows.stride(0), n, E, ptr(order), ptr(seg_offsets), L,
+                                      ptr(out), stream_handle(rows.device)), "ivf_segment_mean")
+    return out
