@@ -679,6 +679,50 @@ int tt_ivf_scan(const void* queries, int q_dtype, int64_t ldq, int64_t M, int E,
                 const int32_t* probes, int nprobe, const int32_t* excl_values, const int64_t* excl_offsets, int k,
                 int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream);
 
+/* An item mask for an IVF index (ABI 4 addition): the catalogue restriction the reference hands its
+ * approximate index (`filters=` of index.similarity_search, 04_evaluate_retrieval.py:97-101). The
+ * list scan reads the mask as a bit per PACKED row in list order; tt_ivf_mask_lists makes it from
+ * the mask over original item indices, with the per-list counts the coarse step needs:
+ *   allow: ceil(N / 32) words over the original item indices, as tt_topk_mips_filtered's (item n is
+ *     eligible iff bit n & 31 of word n >> 5 is set; bits at positions >= N are ignored);
+ *   labels [P], list_begin [L], list_len [L]: the index's, as tt_ivf_scan's;
+ *   row_allow (out): ceil(P / 32) words; bit p is set iff 0 <= labels[p] < N and allow's bit
+ *     labels[p] is set, so a padding row (label -1) is never eligible;
+ *   list_eligible (out): int32 [L], the eligible rows within [list_begin[l], list_begin[l] +
+ *     list_len[l]); 0 for a list that does not lie within the P rows (tt_ivf_scan's condition);
+ *   list_allow (out): ceil(L / 32) words; bit l is set iff list_eligible[l] > 0: tt_topk_mips_filtered's
+ *     `allow` with the centroids as items, so that the coarse step names only lists that hold an
+ *     eligible item.
+ * Every output word is written, those that cover only padding included. Two kernels on `stream` (one
+ * pass over labels, then one over row_allow), no allocation, no synchronisation, integer arithmetic
+ * only: the same inputs give bit-identical outputs. A mask costs P / 8 + L / 8 bytes and shares the
+ * index's rows (a repacked copy would cost P * E * 2).
+ * Limits (TT_EINVAL otherwise, before any launch): 1 <= N < 2^31, 1 <= P < 2^31, 1 <= L <= 2^20, no
+ * NULL pointer. */
+int tt_ivf_mask_lists(const uint32_t* allow, int64_t N, const int32_t* labels, int64_t P, const int64_t* list_begin,
+                      const int32_t* list_len, int64_t L, uint32_t* row_allow, uint32_t* list_allow,
+                      int32_t* list_eligible, void* stream);
+
+/* tt_ivf_scan over each query's ELIGIBLE rows (ABI 4 addition): every argument of tt_ivf_scan in the
+ * same order, and row_allow (tt_ivf_mask_lists' output, ceil(P / 32) words, not NULL) before k.
+ * CONTRACT: ids / scores [M, k] are exactly what tt_topk_mips_filtered returns for the same queries,
+ * the N original rows, their bias and the item mask `allow` that row_allow was made from, when query m
+ * is also denied every item outside its probed lists and its exclusion segment: the same score bits
+ * for the same pairs, the same order (higher score, then lower original index), id -1 / score -inf
+ * where fewer than k items remain, bit-identical across runs and independent of the probes' order.
+ * A denied row never enters a candidate buffer, so it neither raises a query's threshold nor
+ * displaces an eligible item. The chunk's mask words are loaded with its rows and staged beside its
+ * bias; they are whole aligned words because a list begins at a multiple of 32 (the index's lists
+ * begin at multiples of 128). A list whose list_begin is not a multiple of 32 is treated as empty in
+ * this call, as a list that does not lie within the P rows is; no device data causes an
+ * out-of-range access. Workspace (tt_ivf_scan_workspace_bytes), limits, launches (a memset and five
+ * kernels) and status codes are tt_ivf_scan's, each returned before any launch. */
+int tt_ivf_scan_masked(const void* queries, int q_dtype, int64_t ldq, int64_t M, int E, const void* rows,
+                       const float* bias, const int32_t* labels, int64_t P, const int64_t* list_begin,
+                       const int32_t* list_len, int64_t L, const int32_t* probes, int nprobe,
+                       const int32_t* excl_values, const int64_t* excl_offsets, const uint32_t* row_allow, int k,
+                       int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream);
+
 /* The centroid update of the index's k-means (ABI 4 addition): out[l, :] = the mean of
  * rows[order[i], :] over i in [seg_offsets[l], seg_offsets[l + 1]) for each of L segments; rows
  * [n, E] fp32 or bf16 with row stride ld, order [n] int64 (row indices; one outside [0, n) adds

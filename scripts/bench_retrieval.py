@@ -21,6 +21,19 @@ prints each one's ratio to ``fused`` of the same process.
 it prints the build time, each arm's ratio to ``fused`` of the same process and recall@k of the IVF
 ids against the exact ids. --clusters C draws items and queries from a seeded mixture of C Gaussians
 (centres 0.5 N(0, I), --sigma per coordinate): uniform random vectors have no list structure.
+
+    python scripts/bench_retrieval.py --no-baseline --filter --clusters 2048 --ivf 2048 --nprobe 8,32
+
+--ivf with --filter adds the item mask on the index (IVFIndex.restricted: tt_ivf_mask_lists and
+tt_ivf_scan_masked), per value of --nprobe: ``ivf_npP_masked_noop`` (an all-ones mask: the price of
+the masked path; ``..._noop_scan`` is its scan alone, on the probes of ``ivf_npP_scan``),
+``ivf_npP_masked90`` (the seeded ~90 % mask of the ``filtered`` arm, without its seen lists) and, at a
+seeded ~5 % mask, ``ivf_npP_masked5_plain`` (the unrestricted index's probes, masked scan) against
+``ivf_npP_masked5_aware`` (the restricted view's search: probes that count only lists with an
+eligible item); and the same pair at a "department" mask, the items of every 20th list
+(``ivf_npP_maskeddept_plain`` / ``_aware``): a uniform mask leaves an eligible item in every list, a
+structured one empties most of a query's nearest lists. Each arm's recall@k is against the exact ops.topk_mips(allow=) ids of its mask; the
+time of restricted() itself is printed per mask.
 """
 import argparse
 import json
@@ -56,6 +69,15 @@ def timed(fn):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1), out
+
+
+def recall(got, exact):
+    """Share of the exact ids (those >= 0) that `got` holds in the same row."""
+    hit = 0
+    for lo in range(0, exact.shape[0], 1024):
+        e = exact[lo:lo + 1024]
+        hit += int(((got[lo:lo + 1024].unsqueeze(2) == e.unsqueeze(1)).any(1) & (e >= 0)).sum())
+    return round(hit / max(1, int((exact >= 0).sum())), 5)
 
 
 def main():
@@ -128,6 +150,39 @@ def main():
             arms[f"ivf_np{p}_coarse"] = lambda p=p: index.probes(q, p)
             arms[f"ivf_np{p}_scan"] = lambda probes=probes: ops.ivf_scan(
                 q, index.rows, index.labels, index.list_begin, index.list_len, probes, a.k, bias=index.bias)
+        masked_ref, mask_prep_ms = {}, {}
+        if a.filter:
+            mask5 = ops.pack_allow_mask(torch.rand(a.N, device=dev, generator=g) < 0.05)
+            # the items of every 20th list: the row's list from list_begin, the item from its label
+            row_list = torch.searchsorted(index.list_begin, torch.arange(index.labels.numel(), device=dev), right=True) - 1
+            dept_rows = (row_list % 20 == 0) & (index.labels >= 0)
+            dept = torch.zeros(a.N, dtype=torch.bool, device=dev)
+            dept[index.labels[dept_rows].long()] = True
+            maskdept = ops.pack_allow_mask(dept)
+            views = {}
+            for name, words in (("noop", ones), ("90", mask), ("5", mask5), ("dept", maskdept)):
+                index.restricted(words)  # warm-up
+                mask_prep_ms[name], views[name] = timed(lambda words=words: index.restricted(words))
+            masked_ref = {"masked_noop": None, "masked90": ops.topk_mips(q, c, a.k, splits=a.splits, allow=mask)[0],
+                          "masked5_plain": ops.topk_mips(q, c, a.k, splits=a.splits, allow=mask5)[0]}
+            masked_ref["masked5_aware"] = masked_ref["masked5_plain"]
+            masked_ref["maskeddept_plain"] = ops.topk_mips(q, c, a.k, splits=a.splits, allow=maskdept)[0]
+            masked_ref["maskeddept_aware"] = masked_ref["maskeddept_plain"]
+            for p in nprobes:
+                probes = index.probes(q, p)
+                arms[f"ivf_np{p}_masked_noop"] = lambda p=p: views["noop"].search(q, a.k, p)
+                arms[f"ivf_np{p}_masked_noop_scan"] = lambda probes=probes: ops.ivf_scan(
+                    q, index.rows, index.labels, index.list_begin, index.list_len, probes, a.k, bias=index.bias,
+                    row_allow=views["noop"].row_allow)
+                arms[f"ivf_np{p}_masked90"] = lambda p=p: views["90"].search(q, a.k, p)
+                arms[f"ivf_np{p}_masked5_plain"] = lambda p=p: ops.ivf_scan(
+                    q, index.rows, index.labels, index.list_begin, index.list_len, index.probes(q, p), a.k,
+                    bias=index.bias, row_allow=views["5"].row_allow)
+                arms[f"ivf_np{p}_masked5_aware"] = lambda p=p: views["5"].search(q, a.k, p)
+                arms[f"ivf_np{p}_maskeddept_plain"] = lambda p=p: ops.ivf_scan(
+                    q, index.rows, index.labels, index.list_begin, index.list_len, index.probes(q, p), a.k,
+                    bias=index.bias, row_allow=views["dept"].row_allow)
+                arms[f"ivf_np{p}_maskeddept_aware"] = lambda p=p: views["dept"].search(q, a.k, p)
     for _ in range(a.warmup):
         for fn in arms.values():
             fn()
@@ -164,13 +219,22 @@ def main():
         for p in nprobes:
             n = f"ivf_np{p}"
             got = outs[n][0]
-            hit = 0
-            for lo in range(0, a.M, 1024):  # recall@k against the exact ids (which are all >= 0)
-                hit += int((got[lo:lo + 1024].unsqueeze(2) == exact[lo:lo + 1024].unsqueeze(1)).any(2).sum())
-            res[n]["recall_at_k"] = round(hit / exact.numel(), 5)
+            res[n]["recall_at_k"] = recall(got, exact)
             for m in (n, n + "_coarse", n + "_scan"):
                 res[m]["ratio_to_fused"] = round(res[m]["median_ms"] / res["fused"]["median_ms"], 4)
             res[n]["scan_equals_search"] = bool(torch.equal(outs[n + "_scan"][0], got))
+            for arm, ref in masked_ref.items():
+                m = f"{n}_{arm}"
+                res[m]["recall_at_k"] = recall(outs[m][0], exact if ref is None else ref)
+                res[m]["ratio_to_fused"] = round(res[m]["median_ms"] / res["fused"]["median_ms"], 4)
+                res[m]["ratio_to_ivf"] = round(res[m]["median_ms"] / res[n]["median_ms"], 4)
+            if masked_ref:
+                m = n + "_masked_noop"
+                res[m]["equals_ivf"] = bool(torch.equal(outs[m][0], got) and torch.equal(outs[m][1], outs[n][1]))
+                res[m + "_scan"]["ratio_to_ivf_scan"] = round(res[m + "_scan"]["median_ms"] / res[n + "_scan"]["median_ms"], 4)
+        if masked_ref:
+            res["ivf"]["restricted_ms"] = {n: round(t, 3) for n, t in mask_prep_ms.items()}
+            res["ivf"]["eligible"] = {n: int(v.eligible) for n, v in views.items()}
     if not a.no_baseline:
         res["speedup_median"] = round(res["torch"]["median_ms"] / res["fused"]["median_ms"], 2)
         # slowest fused run against the fastest torch run: > 1 means faster by more than the spread

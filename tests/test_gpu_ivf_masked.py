@@ -1,0 +1,487 @@
+"""IVF retrieval with an item mask on the GPU (ops.ivf_mask_lists, ops.ivf_scan(row_allow=),
+IVFIndex.restricted and lifecycle's index= with a restricted view). The oracle is the exact kernel:
+ops.topk_mips with the same item mask and each query's exclusion list set to the ascending complement
+of its probed lists' items (united with its seen items); equality is equal ids and equal score bits."""
+import pytest
+import torch
+
+import ivf_cases as ic
+import retrieval_filter_oracle as fo
+import retrieval_oracle as ro
+
+pytestmark = pytest.mark.gpu
+
+NEG_INF = float("-inf")
+
+
+def _bits(x):
+    return x.contiguous().view(torch.int32)
+
+
+def _assert_same(got, want, what=""):
+    gi, gs, wi, ws = got[0].cpu(), got[1].cpu(), want[0].cpu(), want[1].cpu()
+    assert torch.equal(gi, wi), f"ids differ {what}"
+    assert torch.equal(_bits(gs), _bits(ws)), f"score bits differ {what}"
+
+
+def _index(items, assign, nlist, device, bias=None, metric="dot"):
+    from two_tower_recommender_model_amd.ivf import IVFIndex
+
+    return IVFIndex.from_assignment(items.to(device), assign.to(device), nlist, metric=metric,
+                                    bias=None if bias is None else bias.to(device))
+
+
+def _words(mask, device, garbage=False):
+    """pack_allow_mask's words of a bool [N] mask; garbage: the last word's bits at positions >= N set."""
+    from two_tower_recommender_model_amd import ops
+
+    w = ops.pack_allow_mask(mask.to(device))
+    N = mask.numel()
+    if garbage:
+        assert N % 32, "no bits past N to set"
+        high = ((1 << 32) - 1) ^ ((1 << (N % 32)) - 1)
+        w = w.clone()
+        w[-1] = torch.tensor(high - (1 << 32), dtype=torch.int64).to(torch.int32).to(device) | w[-1]
+    return w
+
+
+def _mask_lists(idx, words):
+    from two_tower_recommender_model_amd import ops
+
+    return ops.ivf_mask_lists(words, idx.N, idx.labels, idx.list_begin, idx.list_len)
+
+
+def _scan(idx, Q, probes, k, device, row_allow=None, exclude=None):
+    from two_tower_recommender_model_amd import ops
+
+    if exclude is not None:
+        exclude = (exclude[0].to(device), exclude[1].to(device))
+    out = ops.ivf_scan(Q.to(device), idx.rows, idx.labels, idx.list_begin, idx.list_len, probes.to(device), k,
+                       bias=idx.bias, exclude=exclude, row_allow=row_allow)
+    torch.cuda.synchronize()
+    return out
+
+
+def _oracle(Q, items, k, device, assign, probes, nlist, mask, bias=None, seen=None, dead_lists=()):
+    """The exact filtered kernel: the item mask, and everything outside the probed lists excluded."""
+    from two_tower_recommender_model_amd import ops
+
+    elig = ic.eligibility_for_probes(assign, probes, nlist, dead_lists)
+    xv, xo = ic.exclusion_from_eligibility(elig, seen)
+    out = ops.topk_mips(Q.to(device), items.to(device), k, bias=None if bias is None else bias.to(device),
+                        allow=_words(mask, device), exclude=(xv.to(device), xo.to(device)))
+    torch.cuda.synchronize()
+    return out
+
+
+def _unpack(words, n):
+    w = words.cpu().to(torch.int64) & 0xFFFFFFFF
+    return ((w.view(-1, 1) >> torch.arange(32)) & 1).flatten()[:n].bool()
+
+
+def _cpu_mask_lists(idx, mask):
+    """(row bits bool [P], list_eligible int64 [L], list bits bool [L]) by the definition, on the CPU.
+    A list that does not lie within the P rows has no eligible row."""
+    labels, begin, length = idx.labels.cpu().long(), idx.list_begin.cpu(), idx.list_len.cpu().long()
+    P = labels.numel()
+    row = (labels >= 0) & (labels < mask.numel()) & mask[labels.clamp(0, mask.numel() - 1)]
+    cnt = torch.zeros(begin.numel(), dtype=torch.int64)
+    for l in range(begin.numel()):
+        b, n = int(begin[l]), int(length[l])
+        if n >= 0 and 0 <= b <= P and n <= P - b:
+            cnt[l] = int(row[b:b + n].sum())
+    return row, cnt, cnt > 0
+
+
+# ---- 1. scan equals filtered exact ------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("with_bias", [False, True], ids=["nobias", "bias"])
+@pytest.mark.parametrize("E", [32, 64, 128])
+def test_masked_scan_equals_filtered_exact(device, E, with_bias):
+    M, N, nlist, k = 40, 3000, 8, 100
+    assert N % 32
+    Q, Cm = ro.make_inputs(M, N, E, 300 + E)
+    g = torch.Generator().manual_seed(E)
+    assign = torch.randint(0, nlist, (N,), generator=g)
+    bias = 0.3 * torch.randn(N, generator=g) if with_bias else None
+    mask = torch.rand(N, generator=torch.Generator().manual_seed(1000 + E)) < 0.5
+    # every list keeps more than k eligible items (a property of the seeds, checked on the CPU)
+    assert (torch.bincount(assign[mask], minlength=nlist) > k).all()
+    idx = _index(Cm, assign, nlist, device, bias=bias)
+    # E = 64: the last word's bits at positions >= N are set and must be ignored
+    row_allow, _, list_eligible = _mask_lists(idx, _words(mask, device, garbage=(E == 64)))
+    assert torch.equal(list_eligible.cpu().long(), torch.bincount(assign[mask], minlength=nlist))
+    for nprobe in (1, 3, 8):
+        probes = ic.distinct_probes(M, nlist, nprobe, 10 * E + nprobe)
+        got = _scan(idx, Q, probes, k, device, row_allow=row_allow)
+        assert (got[0] >= 0).all()
+        assert mask[got[0].cpu()].all()
+        _assert_same(got, _oracle(Q, Cm, k, device, assign, probes, nlist, mask, bias=bias), f"nprobe {nprobe}")
+
+
+# ---- 2. trivial masks -------------------------------------------------------------------------------
+
+
+def test_trivial_masks(device):
+    M, N, E, nlist, nprobe, k = 40, 3000, 64, 8, 3, 100
+    Q, Cm = ro.make_inputs(M, N, E, 21)
+    assign = torch.randint(0, nlist, (N,), generator=torch.Generator().manual_seed(22))
+    idx = _index(Cm, assign, nlist, device)
+    probes = ic.distinct_probes(M, nlist, nprobe, 23)
+
+    ones = _mask_lists(idx, _words(torch.ones(N, dtype=torch.bool), device))
+    assert torch.equal(ones[2].cpu(), idx.list_len.cpu())
+    _assert_same(_scan(idx, Q, probes, k, device, row_allow=ones[0]), _scan(idx, Q, probes, k, device), "(all ones)")
+
+    zeros = _mask_lists(idx, _words(torch.zeros(N, dtype=torch.bool), device))
+    assert (zeros[0] == 0).all() and (zeros[1] == 0).all() and (zeros[2] == 0).all()
+    ids, sc = _scan(idx, Q, probes, k, device, row_allow=zeros[0])
+    assert (ids == -1).all() and (sc == NEG_INF).all()
+
+    item = 1234
+    one = torch.zeros(N, dtype=torch.bool)
+    one[item] = True
+    row_allow, list_allow, list_eligible = _mask_lists(idx, _words(one, device))
+    want_lists = torch.zeros(nlist, dtype=torch.int32)
+    want_lists[assign[item]] = 1
+    assert torch.equal(list_eligible.cpu(), want_lists) and int(list_allow.cpu()[0]) == 1 << int(assign[item])
+    ids, sc = _scan(idx, Q, probes, k, device, row_allow=row_allow)
+    ids, sc = ids.cpu(), sc.cpu()
+    hit = (probes == int(assign[item])).any(1)
+    assert hit.any() and not hit.all()
+    assert (ids[hit, 0] == item).all() and (ids[~hit, 0] == -1).all()
+    assert (ids[:, 1:] == -1).all() and (sc[:, 1:] == NEG_INF).all() and (sc[~hit, 0] == NEG_INF).all()
+    _assert_same((ids, sc), _oracle(Q, Cm, k, device, assign, probes, nlist, one), "(one item)")
+
+
+# ---- 3. word and chunk boundaries ----------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("E", [64, 128])
+def test_word_and_chunk_boundaries(device, E):
+    """Eligible only at chosen positions of one list of 400 rows: the first and last bit of a word, of a
+    chunk (128 rows at E = 64, 64 at E = 128) and of the list."""
+    from two_tower_recommender_model_amd import ops
+
+    M, N, k, nlist = 17, 1037, 256, 3
+    Q, Cm = ro.make_inputs(M, N, E, 31 + E)
+    assign = torch.where(torch.arange(N) < 400, 0, torch.where(torch.arange(N) < 800, 1, 2))
+    idx = _index(Cm, assign, nlist, device)
+    length = int(idx.list_len.cpu()[0])
+    assert length >= 300
+    pos = [0, 31, 32, 63, 64, 127, 128, 129, length - 1]
+    items = idx.labels.cpu()[int(idx.list_begin.cpu()[0]) + torch.tensor(pos)].long()
+    mask = torch.zeros(N, dtype=torch.bool)
+    mask[items] = True
+    row_allow, _, list_eligible = _mask_lists(idx, _words(mask, device))
+    assert list_eligible.cpu().tolist() == [len(pos), 0, 0]
+    probes = torch.tensor([0, 1, 2], dtype=torch.int32).repeat(M, 1)
+    got = _scan(idx, Q, probes, k, device, row_allow=row_allow)
+    want = ops.topk_mips(Q.to(device), Cm.to(device), k, allow=_words(mask, device))
+    _assert_same(got, want)
+    ids = got[0].cpu()
+    assert (ids[:, len(pos):] == -1).all() and (got[1].cpu()[:, len(pos):] == NEG_INF).all()
+    assert (ids[:, :len(pos)].sort(1).values == items.sort().values).all()
+
+
+# ---- 4. short lists, padding, guard words ---------------------------------------------------------------
+
+
+def test_short_lists_padding_and_guard_words(device):
+    from two_tower_recommender_model_amd import _lib
+    from two_tower_recommender_model_amd.ivf import IVFIndex
+
+    lib = _lib.load()
+    M, N, E, nlist, nprobe, k = 40, 3000, 64, 6, 3, 100
+    Q, Cm = ro.make_inputs(M, N, E, 41)
+    g = torch.Generator().manual_seed(42)
+    assign = torch.randint(3, nlist, (N,), generator=g)  # list 0 stays empty
+    small = torch.randperm(N, generator=g)[:128]
+    assign[small[0]] = 1     # one item
+    assign[small[1:]] = 2    # 127 items
+    idx = _index(Cm, assign, nlist, device)
+    assert idx.list_len.cpu().tolist()[:3] == [0, 1, 127]
+    mask = torch.rand(N, generator=g) < 0.5
+    mask[small[0]] = True
+    words = _words(mask, device)
+    P, W, LW = idx.rows.shape[0], (idx.rows.shape[0] + 31) // 32, (nlist + 31) // 32
+    probes = ic.distinct_probes(M, nlist, nprobe, 43)
+    probes[0] = torch.tensor([0, 1, 2])   # only the short ones
+    probes[1] = torch.tensor([0, 5, 4])
+    probes[2] = torch.tensor([0, -1, -1])  # the empty list alone
+
+    row_allow, list_allow, list_eligible = _mask_lists(idx, words)
+    row, cnt, live = _cpu_mask_lists(idx, mask)
+    assert torch.equal(_unpack(row_allow, P), row)
+    assert not _unpack(row_allow, P)[idx.labels.cpu() < 0].any(), "a padding row is eligible"
+    assert torch.equal(list_eligible.cpu().long(), cnt) and cnt[0] == 0 and cnt[1] == 1
+    assert torch.equal(_unpack(list_allow, nlist), live) and _unpack(list_allow, 32)[nlist:].sum() == 0
+    for kk in (256, 1):
+        got = _scan(idx, Q, probes, kk, device, row_allow=row_allow)
+        _assert_same(got, _oracle(Q, Cm, kk, device, assign, probes, nlist, mask), f"k {kk}")
+        assert (got[0][2] == -1).all() and (got[1][2] == NEG_INF).all()
+
+    # a hand-made index: list 2 reaches one row past P, list 4 begins past P (both lie outside the P
+    # rows: no eligible row, no result); list 5 begins at a row that is no multiple of 32: counted by
+    # its rows, and empty for the masked scan
+    begin, length = idx.list_begin.clone(), idx.list_len.clone()
+    length[2] = P - int(begin[2]) + 1
+    begin[4] = P + 128
+    begin[5] += 16
+    length[5] -= 16
+    bad = IVFIndex(idx.centroids, idx.centroid_bias, idx.rows, None, idx.labels, begin, length, "dot", N)
+    _, bad_cnt, bad_live = _cpu_mask_lists(bad, mask)
+    assert bad_cnt[2] == 0 and bad_cnt[4] == 0 and bad_cnt[5] > 0
+    want_bad = _oracle(Q, Cm, k, device, assign, probes, nlist, mask, dead_lists=(2, 4, 5))
+
+    # tt_ivf_mask_lists raw, guard words around its three outputs
+    GUARD, PAD = 0x5A5A5A5A, 8
+    for ix, want_cnt, want_live in ((idx, cnt, live), (bad, bad_cnt, bad_live)):
+        ra = torch.full((W + 2 * PAD,), GUARD, dtype=torch.int32, device=device)
+        la = torch.full((LW + 2 * PAD,), GUARD, dtype=torch.int32, device=device)
+        le = torch.full((nlist + 2 * PAD,), GUARD, dtype=torch.int32, device=device)
+        _lib.check(lib.tt_ivf_mask_lists(words.data_ptr(), N, ix.labels.data_ptr(), P, ix.list_begin.data_ptr(),
+                                         ix.list_len.data_ptr(), nlist, ra[PAD:].data_ptr(), la[PAD:].data_ptr(),
+                                         le[PAD:].data_ptr(), _lib.stream_handle(device)))
+        torch.cuda.synchronize()
+        for t, n in ((ra, W), (la, LW), (le, nlist)):
+            assert (t[:PAD] == GUARD).all() and (t[PAD + n:] == GUARD).all()
+        assert torch.equal(_unpack(ra[PAD:PAD + W], P), row)
+        assert torch.equal(le[PAD:PAD + nlist].cpu().long(), want_cnt)
+        assert torch.equal(_unpack(la[PAD:PAD + LW], nlist), want_live)
+        assert _unpack(la[PAD:PAD + LW], 32)[nlist:].sum() == 0
+
+    # tt_ivf_scan_masked raw, guard words around ids, scores and the workspace
+    q, pr = Q.to(device), probes.to(device)
+    nws = lib.tt_ivf_scan_workspace_bytes(M, nprobe, k, nlist)
+    ids = torch.full((M * k + 32,), -77, dtype=torch.int64, device=device)
+    sc = torch.full((M * k + 32,), -77.0, device=device)
+    ws = torch.full((nws + 256,), 0xAB, dtype=torch.uint8, device=device)
+    want = _oracle(Q, Cm, k, device, assign, probes, nlist, mask)
+    for ix, w in ((idx, want), (bad, want_bad)):
+        _lib.check(lib.tt_ivf_scan_masked(q.data_ptr(), _lib.TT_F32, E, M, E, ix.rows.data_ptr(), None, ix.labels.data_ptr(),
+                                          P, ix.list_begin.data_ptr(), ix.list_len.data_ptr(), nlist, pr.data_ptr(), nprobe,
+                                          None, None, row_allow.data_ptr(), k, ids.data_ptr(), sc.data_ptr(),
+                                          ws.data_ptr(), nws, _lib.stream_handle(device)))
+        torch.cuda.synchronize()
+        assert (ids[M * k:] == -77).all() and (sc[M * k:] == -77.0).all() and (ws[nws:] == 0xAB).all()
+        _assert_same((ids[:M * k].view(M, k), sc[:M * k].view(M, k)), w)
+
+
+# ---- 5. fewer than k eligible --------------------------------------------------------------------------
+
+
+def test_fewer_than_k_eligible(device):
+    M, N, E, nlist, nprobe, k = 40, 3000, 64, 8, 3, 100
+    Q, Cm = ro.make_inputs(M, N, E, 51)
+    g = torch.Generator().manual_seed(52)
+    assign = torch.randint(0, nlist, (N,), generator=g)
+    mask = torch.rand(N, generator=g) < 0.03
+    per_list = torch.bincount(assign[mask], minlength=nlist)
+    assert (per_list > 0).all() and int(per_list.sort().values[-nprobe:].sum()) < k
+    idx = _index(Cm, assign, nlist, device)
+    row_allow = _mask_lists(idx, _words(mask, device))[0]
+    probes = ic.distinct_probes(M, nlist, nprobe, 53)
+    got = _scan(idx, Q, probes, k, device, row_allow=row_allow)
+    _assert_same(got, _oracle(Q, Cm, k, device, assign, probes, nlist, mask))
+    ids, sc = got[0].cpu(), got[1].cpu()
+    n_elig = per_list[probes.long()].sum(1)
+    for m in range(M):
+        n = int(n_elig[m])
+        assert (ids[m, :n] >= 0).all() and (ids[m, n:] == -1).all() and (sc[m, n:] == NEG_INF).all()
+
+
+# ---- 6. the mask and seen lists together ----------------------------------------------------------------
+
+
+def test_mask_and_seen_lists(device):
+    from two_tower_recommender_model_amd import ops
+
+    M, N, E, nlist, k = 130, 3000, 64, 4, 20
+    Q, Cm = ro.make_inputs(M, N, E, 71)
+    g = torch.Generator().manual_seed(72)
+    assign = torch.randint(0, nlist, (N,), generator=g)
+    mask = torch.rand(N, generator=g) < 0.5
+    idx = _index(Cm, assign, nlist, device)
+    row_allow = _mask_lists(idx, _words(mask, device))[0]
+    probes = torch.tensor([0, 1], dtype=torch.int32).repeat(M, 1)
+    probes[129] = torch.tensor([2, 3])  # query 129, the second tile's only pair, alone with its lists
+    plain = _scan(idx, Q, probes, k, device, row_allow=row_allow)[0].cpu()
+    assert (plain >= 0).all()
+    seen = []
+    for m in range(M):
+        rnd = torch.randint(-2, N + 2, (int(torch.randint(0, 60, (1,), generator=g)),), generator=g).tolist()
+        seen.append(plain[m, ::2].tolist() + rnd if m % 7 else [])
+    seen[5] = (((assign == 0) | (assign == 1)) & mask).nonzero().flatten().tolist()  # all it is eligible for
+    seen[129] = plain[129, :15].tolist() + [0, 1, 2]
+    offs = torch.tensor([0] + [len(l) for l in seen], dtype=torch.int64).cumsum(0)
+    vals = ops.sort_exclusions(torch.tensor([x for l in seen for x in l], dtype=torch.int64).to(device), offs.to(device), N)
+    got = _scan(idx, Q, probes, k, device, row_allow=row_allow, exclude=(vals, offs))
+    _assert_same(got, _oracle(Q, Cm, k, device, assign, probes, nlist, mask, seen=seen))
+    ids = got[0].cpu()
+    assert (ids[5] == -1).all()
+    for m in (1, 64, 129):
+        assert not set(ids[m].tolist()) & set(seen[m]) and (ids[m] >= 0).all() and mask[ids[m]].all()
+
+
+# ---- 7. ties ----------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("E", [64, 128])
+def test_duplicate_rows_with_the_lowest_denied(device, E):
+    """test_gpu_ivf's 13 copies of one dominant row; the three of lowest index are denied, k = 10: the
+    other 10 in ascending order, whatever the order of the probes."""
+    M, N, k, nlist = 17, 1037, 10, 3
+    g = torch.Generator().manual_seed(41)
+    u = torch.randn(E, generator=g) * 0.5
+    Q = u + 0.05 * torch.randn(M, E, generator=g)
+    Cm = torch.randn(N, E, generator=g) * 0.5
+    dup = list(range(124, 131)) + list(range(900, 906))
+    Cm[dup] = 2.0 * u
+    assign = torch.where(torch.arange(N) < 400, 0, torch.where(torch.arange(N) < 800, 1, 2))
+    mask = torch.ones(N, dtype=torch.bool)
+    mask[dup[:3]] = False
+    idx = _index(Cm, assign, nlist, device)
+    row_allow = _mask_lists(idx, _words(mask, device))[0]
+    for cols in ([0, 1, 2], [2, 0, 1]):
+        probes = torch.tensor(cols, dtype=torch.int32).repeat(M, 1)
+        ids, sc = _scan(idx, Q, probes, k, device, row_allow=row_allow)
+        assert (ids.cpu() == torch.tensor(dup[3:])).all(), cols
+        assert (sc == sc[:, :1]).all()
+
+
+# ---- 8. list-aware probing -----------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("metric", ["l2", "dot"])
+def test_list_aware_probing(device, metric):
+    from two_tower_recommender_model_amd import lifecycle as lc
+    from two_tower_recommender_model_amd import ops
+    from two_tower_recommender_model_amd.ivf import build_ivf_index
+
+    items, cluster, queries, qcluster, init = ic.mixture()
+    it, q = items.to(device), queries.to(device)
+    idx = build_ivf_index(it, ic.MIX_C, metric=metric, iters=3, init_centroids=it[init.to(device)])
+    # list l is cluster l (test_gpu_ivf.test_mixture_nprobe_1_is_exact asserts the same)
+    labels, begin = idx.labels.cpu(), idx.list_begin.cpu()
+    for l in range(ic.MIX_C):
+        assert (cluster[labels[int(begin[l]):int(begin[l]) + ic.MIX_PER].long()] == l).all()
+    mask = cluster >= 8
+    mask[(cluster == 8).nonzero().flatten()[5:]] = False  # all but 5 items of cluster 8
+    live = 8
+    view = idx.restricted(mask.to(device))
+    for n in idx._TENSORS:
+        a, b = getattr(idx, n), getattr(view, n)
+        assert (a is None and b is None) or a.data_ptr() == b.data_ptr(), f"{n} is not shared"
+    assert view.list_eligible.cpu().tolist() == [0] * 8 + [5] + [ic.MIX_PER] * 7
+    assert int(view.eligible) == int(mask.sum())
+    assert idx.row_allow is None  # the base stays unrestricted
+
+    first = view.probes(q, 1).cpu()
+    assert first.shape == (q.shape[0], 1) and (view.list_eligible.cpu()[first.long()] > 0).all()
+
+    k = 10
+    bias = lc.l2_bias(it) if metric == "l2" else None
+    want = ops.topk_mips(q, it, k, bias=bias, allow=ops.pack_allow_mask(mask.to(device)))
+    assert (want[0] >= 0).all()
+    pr = view.probes(q, live).cpu()
+    assert ((pr >= 8) & (pr < ic.MIX_C)).all() and (pr.sort(1).values == torch.arange(8, 16)).all()
+    _assert_same(view.search(q, k, live), want, "(nprobe = live lists)")
+    more = view.probes(q, live + 4).cpu()
+    assert torch.equal(more[:, :live], pr) and (more[:, live:] == -1).all()
+    _assert_same(view.search(q, k, live + 4), want, "(nprobe above the live lists)")
+    _assert_same(view.search(q, k, 64, query_chunk=16), want, "(nprobe clamped, chunked)")
+
+    # why the coarse step must know the mask: the plain probes of a query of clusters 0..7 name its own,
+    # dead, list, and the masked scan of it finds nothing
+    plain = idx.probes(q, 1)
+    assert torch.equal(plain.cpu()[:, 0].long(), qcluster)
+    ids, sc = ops.ivf_scan(q, idx.rows, idx.labels, idx.list_begin, idx.list_len, plain, k, bias=idx.bias,
+                           row_allow=view.row_allow)
+    dead = qcluster < 8
+    assert (ids.cpu()[dead] == -1).all() and (sc.cpu()[dead] == NEG_INF).all()
+    assert (ids.cpu()[qcluster > 8] >= 0).all()
+
+    # a mask on a view replaces the view's mask: it is applied to the base
+    again = view.restricted((cluster < 8).to(device))
+    assert again.list_eligible.cpu().tolist() == [ic.MIX_PER] * 8 + [0] * 8
+
+
+# ---- 9. lifecycle -------------------------------------------------------------------------------------
+
+
+def _same_metrics(a, b, path=""):
+    if isinstance(a, dict):
+        assert isinstance(b, dict) and set(a) == set(b), path
+        for name in a:
+            _same_metrics(a[name], b[name], f"{path}/{name}")
+        return
+    a, b = torch.as_tensor(a).cpu().double(), torch.as_tensor(b).cpu().double()
+    assert a.shape == b.shape and torch.equal(torch.isnan(a), torch.isnan(b)), path
+    assert torch.equal(torch.nan_to_num(a), torch.nan_to_num(b)), path
+
+
+@pytest.mark.parametrize("metric", ["dot", "l2"])
+def test_lifecycle_with_a_restricted_index(device, metric):
+    from two_tower_recommender_model_amd import lifecycle as lc
+    from two_tower_recommender_model_amd.fused import FusedTwoTowerStep
+    from two_tower_recommender_model_amd.ivf import build_ivf_index
+
+    N, D, layers, k, U, nlist = [500, 700], 32, [32, 32], 20, 150, 8
+    st = FusedTwoTowerStep(N, [D, D], [0], [1], layers, 64, device, seed=9)
+    g = torch.Generator().manual_seed(91)
+    for t in (0, 1):
+        st.tables.table_view(t).copy_((torch.randn(N[t], D, generator=g) * 0.5).to(device))
+    user_rows = torch.randperm(N[0], generator=g)[:U]
+    item_emb = lc.export_fused(st, "candidate")[1]
+    allow = torch.rand(N[1], generator=g) < 0.6
+    base = lc.retrieve_fused(st, user_rows, k=k, metric=metric, item_emb=item_emb, allow=allow)[0].cpu()
+    seen, targets = [], []
+    for u in range(U):
+        rnd = (torch.randint(0, N[1], (int(torch.randint(0, 50, (1,), generator=g)),), generator=g) + 1).tolist()
+        seen.append([] if u % 7 == 0 else base[u, :k // 2:2].tolist() + rnd + [0, N[1] + 1, -3])
+        cand = (torch.randperm(N[1], generator=g)[:int(torch.randint(0, 30, (1,), generator=g))] + 1).tolist()
+        targets.append((set(cand) | set(base[u, 1:k:4].tolist())) - set(seen[u]))
+    sv, so = fo.csr(seen)
+    tv = torch.tensor([v for t in targets for v in sorted(t)], dtype=torch.int64)
+    to = torch.tensor([0] + [len(t) for t in targets], dtype=torch.int64).cumsum(0)
+
+    idx = build_ivf_index(item_emb, nlist, metric=metric, iters=2)
+    view = idx.restricted(allow)
+    kw = dict(k=k, metric=metric, seen_values=sv, seen_offsets=so)
+    want = lc.retrieve_fused(st, user_rows, item_emb=item_emb, allow=allow, **kw)
+    assert allow[want[0].cpu()[want[0].cpu() > 0] - 1].all()
+    _assert_same(lc.retrieve_fused(st, user_rows, index=view, nprobe=nlist, **kw), want)
+    _assert_same(lc.retrieve_fused(st, user_rows, index=view, nprobe=nlist, query_chunk=16, **kw), want, "(chunked)")
+    _assert_same(lc.retrieve_fused(st, user_rows, index=idx.restricted(_words(allow, device)), nprobe=nlist, **kw), want,
+                 "(packed words)")
+    m_exact = lc.evaluate_retrieval(st, user_rows, tv, to, item_emb=item_emb, allow=allow, **kw)
+    m_index = lc.evaluate_retrieval(st, user_rows, tv, to, index=view, nprobe=nlist, **kw)
+    _same_metrics(m_exact, m_index)
+    _same_metrics(m_exact, lc.evaluate_retrieval(st, user_rows, tv, to, index=view, nprobe=nlist, query_chunk=16, **kw))
+
+
+# ---- 10. determinism ----------------------------------------------------------------------------------
+
+
+def test_determinism(device):
+    M, N, E, nlist, nprobe, k = 150, 3000, 64, 8, 5, 100
+    Q, Cm = ro.make_inputs(M, N, E, 81)
+    g = torch.Generator().manual_seed(82)
+    assign = torch.randint(0, nlist, (N,), generator=g)
+    mask = torch.rand(N, generator=g) < 0.4
+    idx = _index(Cm, assign, nlist, device)
+    a, b = idx.restricted(mask.to(device)), idx.restricted(mask.to(device))
+    for n in ("row_allow", "list_allow", "list_eligible", "eligible"):
+        x, y = getattr(a, n), getattr(b, n)
+        assert x.dtype == y.dtype and torch.equal(x, y), n
+    q = Q.to(device)
+    first = a.search(q, k, nprobe)
+    _assert_same(b.search(q, k, nprobe), first, "(repeat)")
+    probes = a.probes(q, nprobe).cpu()
+    _assert_same(_scan(idx, Q, probes, k, device, row_allow=a.row_allow), first, "(scan of the same probes)")
+    for _ in range(2):
+        perm = torch.rand(M, nprobe, generator=g).argsort(1)
+        _assert_same(_scan(idx, Q, probes.gather(1, perm).contiguous(), k, device, row_allow=b.row_allow), first,
+                     "(permuted probes)")

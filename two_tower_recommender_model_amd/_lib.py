@@ -333,6 +333,9 @@ SIGNATURES = {
     "tt_ivf_scan_workspace_bytes": (_sz, [_i64, _int, _int, _i64]),
     "tt_ivf_scan": (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp, _vp, _int,
                            _vp, _vp, _vp, _sz, _vp]),
+    "tt_ivf_scan_masked": (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp, _vp,
+                                  _vp, _int, _vp, _vp, _vp, _sz, _vp]),
+    "tt_ivf_mask_lists": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     "tt_ivf_segment_mean": (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp]),
     "tt_table_alloc": (_int, [_sz, _pvp, C.POINTER(C.c_int)]),
     "tt_table_free": (_int, [_vp]),
@@ -397,7 +400,7 @@ COMPUTE_ENTRY_POINTS = [
 ]
 # later ABI 4 additions (csrc/ivf.hip): bound through SIGNATURES like the rest, not part of the
 # count above, which tt_num_entry_points() pins at the entry points up to tt_topk_mips_filtered
-IVF_ENTRY_POINTS = ["tt_ivf_scan", "tt_ivf_segment_mean"]
+IVF_ENTRY_POINTS = ["tt_ivf_scan", "tt_ivf_segment_mean", "tt_ivf_mask_lists", "tt_ivf_scan_masked"]
 
 _lib = None
 _lock = threading.Lock()

@@ -62,7 +62,8 @@ int tt_abi_version(void) { return TT_ABI_VERSION; }
 // tt_table_prefault
 // tt_topk_mips
 // tt_topk_mips_filtered
-// (tt_ivf_scan and tt_ivf_segment_mean, later ABI 4 additions, are not counted: the count of the
+// (tt_ivf_scan, tt_ivf_segment_mean, tt_ivf_mask_lists and tt_ivf_scan_masked, later ABI 4
+// additions, are not counted: the count of the
 // entry points above is pinned by the callers that check it)
 int tt_num_entry_points(void) { return 55; }
 

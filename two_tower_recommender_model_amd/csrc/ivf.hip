@@ -23,6 +23,12 @@
 //
 // Nothing the device reads can send an access out of range: a probe outside [0, L) is no probe, a
 // list that does not lie within the P rows is empty, and the grouping writes only slots it counted.
+//
+// The item mask (tt_ivf_scan_masked): a bit per PACKED row, row_allow, which tt_ivf_mask_lists makes
+// from the mask over original item indices and the labels. A list begins at a multiple of 128, so a
+// chunk's bits are whole aligned words: they are loaded with the chunk's other global loads, staged
+// beside its bias, read with the tile's other LDS reads and ANDed into the candidate test, as the
+// exact kernel does with its mask. A denied row never enters a candidate buffer.
 #include "tt_common.h"
 #include "topk_common.h"
 
@@ -155,13 +161,20 @@ struct IvfArgs {
   int k, L, q_bf16;
 };
 
-template <int KS, bool BIAS, bool FILT>
-__global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a) {
+// the MASK instantiations' arguments: ceil(P / 32) words, bit p & 31 of word p >> 5: row p is eligible
+struct IvfMaskArgs : IvfArgs {
+  const uint32_t* row_allow;
+};
+
+template <int KS, bool BIAS, bool FILT, bool MASK>
+__global__ void __launch_bounds__(TK_THREADS, 2)
+    ivf_scan_kernel(const std::conditional_t<MASK, IvfMaskArgs, IvfArgs> a) {
   constexpr int E = KS * 32, STRIDE = E + 8, GPR = E / 8;  // GPR: 8-element groups per item row
   constexpr int TK_IC = tk_chunk(E);
   constexpr int GPT = TK_IC * GPR / TK_THREADS;             // groups per thread
   __shared__ __attribute__((aligned(16))) __bf16 items[2][TK_IC * STRIDE];
   __shared__ __attribute__((aligned(16))) float bias_s[2][TK_IC];
+  __shared__ uint32_t mask_s[2][4];  // MASK: the chunk's TK_IC / 32 mask words (no LDS without MASK)
   __shared__ u64 cbuf_s[TK_WAVES][TK_QW * TK_CB];
   __shared__ u64 lscr_s[TK_WAVES][TT_TOPK_MAX_K];
   __shared__ int ccnt_s[TK_WAVES][TK_QW];
@@ -195,6 +208,13 @@ __global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a
     n_beg = 0;
     len = 0;
   }
+  // MASK: so is a list whose rows' bits are not whole words
+  if constexpr (MASK) {
+    if (n_beg & 31) {
+      n_beg = 0;
+      len = 0;
+    }
+  }
   const int64_t n_end = n_beg + len;
   const int nchunks = (len + TK_IC - 1) / TK_IC;
   const int k = a.k;
@@ -214,6 +234,10 @@ __global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a
   }
   // FILT: does any of the wave's queries have a non-empty exclusion segment?
   const bool wave_excl = FILT && __ballot(lane_excl) != 0ull;
+  // FILT + MASK: the exclusion values' address is held in vector registers, where the call of
+  // topk_drop_excluded wants it anyway: with the mask the scalar registers do not suffice
+  const int32_t* excl_values = a.excl_values;
+  if constexpr (FILT && MASK) asm volatile("" : "+v"(excl_values));
   wave_sync();
 
   // the wave's queries as B operands: lane l holds query (l & 15), k = 32 ks + 8 (l >> 4) + j
@@ -244,6 +268,18 @@ __global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a
   // The rows are bf16 already: 16-byte loads, stored as they are
   bf16x8 rawb[GPT];
   float rawbias = 0.f;
+  uint32_t rawmask = 0u;
+  // MASK: thread t stages word t % (TK_IC / 32) of a chunk (every thread one, without a branch: the
+  // FILT instantiations have no scalar register left for one more saved exec mask). Its index within
+  // the list's words (n_beg is a multiple of 32) is clamped to the list's last word: a word that
+  // begins at or past n_end is not read and counts as zero
+  constexpr int MW = TK_IC / 32;
+  const int mask_i = tid & (MW - 1), mask_last = (len - 1) >> 5;
+  const uint32_t* mask_p = nullptr;
+  if constexpr (MASK) {
+    mask_p = a.row_allow + (n_beg >> 5);
+    asm volatile("" : "+v"(mask_p));  // held in vector registers, for the same reason
+  }
   auto load_chunk = [&](int c) {
     const int64_t n0 = n_beg + (int64_t)c * TK_IC;
 #pragma unroll
@@ -257,6 +293,11 @@ __global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a
       rawb[i] = n < n_end ? *reinterpret_cast<const bf16x8*>(a.rows + n * E + kc) : z;
     }
     if (BIAS && tid < TK_IC) rawbias = n0 + tid < n_end ? a.bias[n0 + tid] : 0.f;
+    if constexpr (MASK) {
+      const int wd = c * MW + mask_i;  // load_chunk runs only where len > 0: mask_last >= 0
+      const uint32_t x = mask_p[min(wd, mask_last)];
+      rawmask = wd <= mask_last ? x : 0u;
+    }
   };
   auto store_chunk = [&](int buf) {
 #pragma unroll
@@ -266,6 +307,9 @@ __global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a
       *reinterpret_cast<bf16x8*>(&items[buf][row * STRIDE + kc]) = rawb[i];
     }
     if (BIAS && tid < TK_IC) bias_s[buf][tid] = rawbias;
+    if constexpr (MASK) {
+      mask_s[buf][mask_i] = rawmask;  // the threads of one word store the same value
+    }
   };
 
   if (nchunks > 0) {
@@ -288,6 +332,10 @@ __global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a
           af[ks] = *reinterpret_cast<const bf16x8*>(&items[buf][(it * 16 + (lane & 15)) * STRIDE + ks * 32 + (lane >> 4) * 8]);
         f32x4 bv = (f32x4)(0.f);
         if (BIAS) bv = *reinterpret_cast<const f32x4*>(&bias_s[buf][it * 16 + (lane >> 4) * 4]);
+        // MASK: the chunk's mask word it >> 1, read with the tile's other LDS reads: not one more
+        // latency inside the candidate branch
+        uint32_t mword = 0u;
+        if constexpr (MASK) mword = mask_s[buf][it >> 1];
 #pragma unroll
         for (int qt = 0; qt < 2; ++qt) {
           f32x4 acc = (f32x4)(0.f);
@@ -302,9 +350,19 @@ __global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a
             const int64_t nb = n0 + it * 16 + (lane >> 4) * 4;
             bool pass[4];
             int cnt = 0;
+            // MASK: the lane's 4 rows are bits (it & 1) * 16 + (lane >> 4) * 4 + r of the word. The
+            // empty asm keeps the shift and the bit tests here, out of the tiles without candidates
+            // (retrieval.hip)
+            uint32_t mbits = 0xfu;
+            if constexpr (MASK) {
+              uint32_t mw = mword;
+              asm volatile("" : "+v"(mw));
+              mbits = mw >> ((it & 1) * 16 + (lane >> 4) * 4);
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               pass[r] = acc[r] > thr[qt] && nb + r < n_end;
+              if constexpr (MASK) pass[r] = pass[r] && ((mbits >> r) & 1u);
               cnt += pass[r] ? 1 : 0;
             }
             const int c16 = __shfl_xor(cnt, 16, 64);
@@ -321,7 +379,7 @@ __global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a
               if constexpr (FILT) {
                 if (wave_excl) {
                   const int mq = __builtin_amdgcn_readfirstlane(qid[qi]);
-                  if (topk_drop_excluded(w, qi, a.excl_values, a.excl_offsets + mq, lane) == 0)
+                  if (topk_drop_excluded(w, qi, excl_values, a.excl_offsets + mq, lane) == 0)
                     continue;  // nothing left to merge, and the buffer is empty
                 }
               }
@@ -351,7 +409,7 @@ __global__ void __launch_bounds__(TK_THREADS, 2) ivf_scan_kernel(const IvfArgs a
     if constexpr (FILT) {
       if (w.ccnt[q] > 0 && wave_excl) {
         const int mq = __builtin_amdgcn_readfirstlane(qid[q]);
-        if (mq >= 0) topk_drop_excluded(w, q, a.excl_values, a.excl_offsets + mq, lane);
+        if (mq >= 0) topk_drop_excluded(w, q, excl_values, a.excl_offsets + mq, lane);
       }
     }
     if (w.ccnt[q] > 0) topk_merge_query(w, q, gl, k, lane);
@@ -391,21 +449,21 @@ __global__ void __launch_bounds__(TK_THREADS) ivf_merge_kernel(const u64* __rest
   }
 }
 
-template <int KS, bool FILT>
-static void ivf_launch(const IvfArgs& a, unsigned blocks, hipStream_t st) {
+template <int KS, bool FILT, bool MASK>
+static void ivf_launch(const IvfMaskArgs& a, unsigned blocks, hipStream_t st) {
   if (a.bias)
-    hipLaunchKernelGGL((ivf_scan_kernel<KS, true, FILT>), dim3(blocks), dim3(TK_THREADS), 0, st, a);
+    hipLaunchKernelGGL((ivf_scan_kernel<KS, true, FILT, MASK>), dim3(blocks), dim3(TK_THREADS), 0, st, a);
   else
-    hipLaunchKernelGGL((ivf_scan_kernel<KS, false, FILT>), dim3(blocks), dim3(TK_THREADS), 0, st, a);
+    hipLaunchKernelGGL((ivf_scan_kernel<KS, false, FILT, MASK>), dim3(blocks), dim3(TK_THREADS), 0, st, a);
 }
 
-template <bool FILT>
-static void ivf_launch_e(const IvfArgs& a, int E, unsigned blocks, hipStream_t st) {
+template <bool FILT, bool MASK>
+static void ivf_launch_e(const IvfMaskArgs& a, int E, unsigned blocks, hipStream_t st) {
   switch (E / 32) {
-    case 1: ivf_launch<1, FILT>(a, blocks, st); break;
-    case 2: ivf_launch<2, FILT>(a, blocks, st); break;
-    case 3: ivf_launch<3, FILT>(a, blocks, st); break;
-    default: ivf_launch<4, FILT>(a, blocks, st); break;
+    case 1: ivf_launch<1, FILT, MASK>(a, blocks, st); break;
+    case 2: ivf_launch<2, FILT, MASK>(a, blocks, st); break;
+    case 3: ivf_launch<3, FILT, MASK>(a, blocks, st); break;
+    default: ivf_launch<4, FILT, MASK>(a, blocks, st); break;
   }
 }
 
@@ -416,6 +474,70 @@ static const char* ivf_check(int64_t M, int nprobe, int k, int64_t L) {
   if (L < 1 || L > IVF_MAX_L) return "L must be in [1, 2^20]";
   if (M >= ((int64_t)1 << 31) / nprobe) return "M * nprobe must be < 2^31";
   return nullptr;
+}
+
+// ---- the item mask in list order ---------------------------------------------------------------
+
+constexpr int IVF_MASK_LISTS_PER_WG = 32;  // one word of list_allow per workgroup
+
+// row_allow: a lane per packed row, a wave per two words. Bit p = the row's label is an item in
+// [0, N) whose bit in `allow` is set; rows past P are no rows. Every word is written.
+__global__ void __launch_bounds__(256) ivf_row_allow_kernel(const uint32_t* __restrict__ allow, int64_t N,
+                                                            const int32_t* __restrict__ labels, int64_t P,
+                                                            uint32_t* __restrict__ row_allow) {
+  const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  bool ok = false;
+  if (p < P) {
+    const int n = labels[p];
+    if (n >= 0 && (int64_t)n < N) ok = (allow[n >> 5] >> (n & 31)) & 1u;
+  }
+  const u64 bits = __ballot(ok);
+  const int lane = threadIdx.x & 63;
+  const int64_t wd = (p >> 6) * 2 + (lane >> 5), words = (P + 31) >> 5;
+  if ((lane & 31) == 0 && wd < words) row_allow[wd] = (uint32_t)(bits >> (lane & 32));
+}
+
+// list_eligible / list_allow from row_allow: a workgroup per 32 lists (one word of list_allow), each of
+// its 4 waves counts 8 of them, a lane per word of the list's rows; integer sums, so any order gives
+// the same count. A list that does not lie within the P rows has no eligible row (ivf_scan_kernel).
+__global__ void __launch_bounds__(TK_THREADS) ivf_list_eligible_kernel(const uint32_t* __restrict__ row_allow,
+                                                                       int64_t P,
+                                                                       const int64_t* __restrict__ list_begin,
+                                                                       const int32_t* __restrict__ list_len, int L,
+                                                                       int32_t* __restrict__ list_eligible,
+                                                                       uint32_t* __restrict__ list_allow) {
+  __shared__ int cnt_s[IVF_MASK_LISTS_PER_WG];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  constexpr int PER_WAVE = IVF_MASK_LISTS_PER_WG / TK_WAVES;
+  for (int i = 0; i < PER_WAVE; ++i) {
+    const int j = wid * PER_WAVE + i;
+    const int l = (int)blockIdx.x * IVF_MASK_LISTS_PER_WG + j;
+    int cnt = 0;
+    if (l < L) {
+      int64_t beg = list_begin[l];
+      int len = list_len[l];
+      if (len < 0 || beg < 0 || beg > P || (int64_t)len > P - beg) len = 0;
+      if (len > 0) {
+        const int64_t end = beg + len;  // <= P: the words below are within ceil(P / 32)
+        const int64_t w0 = beg >> 5, w1 = (end - 1) >> 5;
+        for (int64_t wd = w0 + lane; wd <= w1; wd += 64) {
+          uint32_t x = row_allow[wd];
+          if (wd == w0) x &= 0xffffffffu << (beg & 31);
+          if (wd == w1) x &= 0xffffffffu >> (31 - ((end - 1) & 31));
+          cnt += __popc(x);
+        }
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+      if (lane == 0) list_eligible[l] = cnt;
+    }
+    if (lane == 0) cnt_s[j] = cnt;
+  }
+  __syncthreads();
+  if (wid == 0) {
+    const u64 bits = __ballot(lane < IVF_MASK_LISTS_PER_WG && cnt_s[lane & (IVF_MASK_LISTS_PER_WG - 1)] > 0);
+    if (lane == 0) list_allow[blockIdx.x] = (uint32_t)bits;
+  }
 }
 
 // ---- the centroid update -----------------------------------------------------------------------
@@ -468,12 +590,18 @@ size_t tt_ivf_scan_workspace_bytes(int64_t M, int nprobe, int k, int64_t L) {
   return tt::ivf_ws_layout(M * nprobe, k, L, nullptr, nullptr);
 }
 
-int tt_ivf_scan(const void* queries, int q_dtype, int64_t ldq, int64_t M, int E, const void* rows, const float* bias,
-                const int32_t* labels, int64_t P, const int64_t* list_begin, const int32_t* list_len, int64_t L,
-                const int32_t* probes, int nprobe, const int32_t* excl_values, const int64_t* excl_offsets, int k,
-                int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream) {
-  using namespace tt;
-  const std::string fn = "tt_ivf_scan: ";
+}  // extern "C"
+
+namespace tt {
+
+// tt_ivf_scan (row_allow NULL, masked false) and tt_ivf_scan_masked
+static int ivf_scan_impl(const char* name, bool masked, const void* queries, int q_dtype, int64_t ldq, int64_t M, int E,
+                         const void* rows, const float* bias, const int32_t* labels, int64_t P,
+                         const int64_t* list_begin, const int32_t* list_len, int64_t L, const int32_t* probes,
+                         int nprobe, const int32_t* excl_values, const int64_t* excl_offsets,
+                         const uint32_t* row_allow, int k, int64_t* ids, float* scores, void* workspace,
+                         size_t ws_bytes, void* stream) {
+  const std::string fn = std::string(name) + ": ";
   if (E < 32 || E > 128 || (E & 31)) return fail(TT_EINVAL, fn + "E must be a multiple of 32 in [32, 128]");
   if (const char* msg = ivf_check(M, nprobe, k, L)) return fail(TT_EINVAL, fn + msg);
   if (P < 1 || P >= (int64_t)1 << 31) return fail(TT_EINVAL, fn + "P must be in [1, 2^31)");
@@ -481,6 +609,7 @@ int tt_ivf_scan(const void* queries, int q_dtype, int64_t ldq, int64_t M, int E,
   if (ldq < E) return fail(TT_EINVAL, fn + "ldq must be >= E");
   if (!queries || !rows || !labels || !list_begin || !list_len || !probes || !ids || !scores || !workspace)
     return fail(TT_EINVAL, fn + "null queries / rows / labels / list_begin / list_len / probes / ids / scores / workspace");
+  if (masked && !row_allow) return fail(TT_EINVAL, fn + "null row_allow");
   if ((excl_values == nullptr) != (excl_offsets == nullptr))
     return fail(TT_EINVAL, fn + "excl_values and excl_offsets must both be NULL or both be given");
   if (reinterpret_cast<uintptr_t>(rows) & 15) return fail(TT_EINVAL, fn + "rows must be 16-byte aligned");
@@ -491,15 +620,15 @@ int tt_ivf_scan(const void* queries, int q_dtype, int64_t ldq, int64_t M, int E,
   hipStream_t st = as_stream(stream);
 
   // grouping: count, scan, scatter
-  if (hipMemsetAsync(w.cnt, 0, (size_t)L * 8, st) != hipSuccess) return check_launch("tt_ivf_scan memset");
+  if (hipMemsetAsync(w.cnt, 0, (size_t)L * 8, st) != hipSuccess) return check_launch((fn + "memset").c_str());
   const unsigned pblocks = (unsigned)ceil_div(PN, 256);
   hipLaunchKernelGGL(ivf_count_kernel, dim3(pblocks), dim3(256), 0, st, probes, PN, (int)L, w.cnt);
   hipLaunchKernelGGL(ivf_offsets_kernel, dim3(1), dim3(IVF_SCAN_THREADS), 0, st, w.cnt, (int)L, w.list_off, w.tile_off);
   hipLaunchKernelGGL(ivf_scatter_kernel, dim3(pblocks), dim3(256), 0, st, probes, PN, nprobe, (int)L, w.list_off,
                      w.cursor, w.pair_query, w.slot_of);
-  if (int rc = check_launch("tt_ivf_scan grouping")) return rc;
+  if (int rc = check_launch((fn + "grouping").c_str())) return rc;
 
-  IvfArgs a{};
+  IvfMaskArgs a{};
   a.q = queries;
   a.rows = reinterpret_cast<const unsigned short*>(rows);
   a.bias = bias;
@@ -518,16 +647,65 @@ int tt_ivf_scan(const void* queries, int q_dtype, int64_t ldq, int64_t M, int E,
   a.k = k;
   a.L = (int)L;
   a.q_bf16 = q_dtype == TT_BF16;
+  a.row_allow = row_allow;
   // an upper bound of sum_l ceil(cnt_l / 128): full tiles, plus one partial tile per probed list
   const unsigned blocks = (unsigned)(ceil_div(PN, TK_QB) + std::min<int64_t>(L, PN));
-  if (excl_offsets)
-    ivf_launch_e<true>(a, E, blocks, st);
-  else
-    ivf_launch_e<false>(a, E, blocks, st);
-  if (int rc = check_launch("tt_ivf_scan")) return rc;
+  if (masked) {
+    if (excl_offsets)
+      ivf_launch_e<true, true>(a, E, blocks, st);
+    else
+      ivf_launch_e<false, true>(a, E, blocks, st);
+  } else {
+    if (excl_offsets)
+      ivf_launch_e<true, false>(a, E, blocks, st);
+    else
+      ivf_launch_e<false, false>(a, E, blocks, st);
+  }
+  if (int rc = check_launch((fn + "list scan").c_str())) return rc;
   hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)ceil_div(M, TK_WAVES)), dim3(TK_THREADS), 0, st, w.lists,
                      w.slot_of, M, nprobe, k, ids, scores);
-  return check_launch("tt_ivf_scan merge");
+  return check_launch((fn + "merge").c_str());
+}
+
+}  // namespace tt
+
+extern "C" {
+
+int tt_ivf_scan(const void* queries, int q_dtype, int64_t ldq, int64_t M, int E, const void* rows, const float* bias,
+                const int32_t* labels, int64_t P, const int64_t* list_begin, const int32_t* list_len, int64_t L,
+                const int32_t* probes, int nprobe, const int32_t* excl_values, const int64_t* excl_offsets, int k,
+                int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream) {
+  return tt::ivf_scan_impl("tt_ivf_scan", false, queries, q_dtype, ldq, M, E, rows, bias, labels, P, list_begin,
+                           list_len, L, probes, nprobe, excl_values, excl_offsets, nullptr, k, ids, scores, workspace,
+                           ws_bytes, stream);
+}
+
+int tt_ivf_scan_masked(const void* queries, int q_dtype, int64_t ldq, int64_t M, int E, const void* rows,
+                       const float* bias, const int32_t* labels, int64_t P, const int64_t* list_begin,
+                       const int32_t* list_len, int64_t L, const int32_t* probes, int nprobe,
+                       const int32_t* excl_values, const int64_t* excl_offsets, const uint32_t* row_allow, int k,
+                       int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream) {
+  return tt::ivf_scan_impl("tt_ivf_scan_masked", true, queries, q_dtype, ldq, M, E, rows, bias, labels, P, list_begin,
+                           list_len, L, probes, nprobe, excl_values, excl_offsets, row_allow, k, ids, scores, workspace,
+                           ws_bytes, stream);
+}
+
+int tt_ivf_mask_lists(const uint32_t* allow, int64_t N, const int32_t* labels, int64_t P, const int64_t* list_begin,
+                      const int32_t* list_len, int64_t L, uint32_t* row_allow, uint32_t* list_allow,
+                      int32_t* list_eligible, void* stream) {
+  using namespace tt;
+  const std::string fn = "tt_ivf_mask_lists: ";
+  if (N < 1 || N >= (int64_t)1 << 31) return fail(TT_EINVAL, fn + "N must be in [1, 2^31)");
+  if (P < 1 || P >= (int64_t)1 << 31) return fail(TT_EINVAL, fn + "P must be in [1, 2^31)");
+  if (L < 1 || L > IVF_MAX_L) return fail(TT_EINVAL, fn + "L must be in [1, 2^20]");
+  if (!allow || !labels || !list_begin || !list_len || !row_allow || !list_allow || !list_eligible)
+    return fail(TT_EINVAL, fn + "null allow / labels / list_begin / list_len / row_allow / list_allow / list_eligible");
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(ivf_row_allow_kernel, dim3((unsigned)ceil_div(P, 256)), dim3(256), 0, st, allow, N, labels, P,
+                     row_allow);
+  hipLaunchKernelGGL(ivf_list_eligible_kernel, dim3((unsigned)ceil_div(L, IVF_MASK_LISTS_PER_WG)), dim3(TK_THREADS), 0,
+                     st, row_allow, P, list_begin, list_len, (int)L, list_eligible, list_allow);
+  return check_launch("tt_ivf_mask_lists");
 }
 
 int tt_ivf_segment_mean(const void* rows, int dtype, int64_t ld, int64_t n, int E, const int64_t* order,

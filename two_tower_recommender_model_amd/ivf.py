@@ -7,6 +7,11 @@ coarse step is ops.topk_mips with the centroids as items, the fine step ops.ivf_
 (tt_ivf_scan). A pair's score is the exact kernel's, so a search returns exactly what
 ops.topk_mips returns when the query is denied every item outside its probed lists, bit for bit;
 with nprobe = nlist it is the exact result.
+
+An item mask (the index's ``filters=`` of 04_evaluate_retrieval.py:97-101) is a view of the index:
+IVFIndex.restricted(allow) shares every tensor of the base and adds the mask in list order
+(ops.ivf_mask_lists). Its coarse step names only lists that hold an eligible item, its fine step is
+tt_ivf_scan_masked: exactly ops.topk_mips(allow=...) over the probed lists' items.
 """
 from __future__ import annotations
 
@@ -32,7 +37,12 @@ class IVFIndex:
     bias in the same order; for metric "l2" l2_bias(item_emb) permuted), ``labels`` int32 [P] (the
     original item row, -1 on padding rows), ``list_begin`` int64 [L], ``list_len`` int32 [L],
     ``metric`` and ``N``. Every list_begin is a multiple of 128, lists do not overlap, labels ascend
-    within a list, every item is in exactly one list."""
+    within a list, every item is in exactly one list.
+
+    A view made by ``restricted(allow)`` also carries ``row_allow`` int32 [ceil(P / 32)] (a bit per
+    packed row), ``list_allow`` int32 [ceil(L / 32)] (a bit per list with an eligible row),
+    ``list_eligible`` int32 [L] and ``eligible`` (a 0-d int64 tensor: the eligible items, for the
+    caller to report); they are None on an unrestricted index."""
 
     _TENSORS = ("centroids", "centroid_bias", "rows", "bias", "labels", "list_begin", "list_len")
 
@@ -43,6 +53,7 @@ class IVFIndex:
         self.rows, self.bias, self.labels = rows, bias, labels
         self.list_begin, self.list_len = list_begin, list_len
         self.metric, self.N = metric, int(N)
+        self.row_allow = self.list_allow = self.list_eligible = self.eligible = None
 
     @property
     def nlist(self) -> int:
@@ -89,7 +100,32 @@ class IVFIndex:
         centroids = centroids.to(device=dev, dtype=torch.float32).contiguous()
         return cls(centroids, _l2_bias(centroids), rows, pbias, labels, begin, counts.to(torch.int32), metric, N)
 
+    def restricted(self, allow: torch.Tensor) -> "IVFIndex":
+        """A view of this index restricted to the items ``allow`` admits (bool [N] over the item
+        rows, or ops.pack_allow_mask's int32 words). It shares all seven tensors of the base index
+        (no row is copied: a mask costs P / 8 + L / 8 bytes) and carries the mask in list order.
+        restricted() of a restricted view applies the new mask to the base: masks are not ANDed."""
+        if not isinstance(allow, torch.Tensor) or allow.dim() != 1:
+            raise ValueError("allow must be bool [N] or ops.pack_allow_mask's int32 words")
+        if allow.dtype == torch.bool:
+            if allow.numel() != self.N:
+                raise ValueError(f"allow must have N = {self.N} entries, not {allow.numel()}")
+        elif allow.dtype == torch.int32:
+            if allow.numel() != (self.N + 31) // 32:
+                raise ValueError(f"allow must have ceil(N / 32) = {(self.N + 31) // 32} words, not {allow.numel()}")
+        else:
+            raise ValueError("allow must be bool [N] or ops.pack_allow_mask's int32 words")
+        allow = allow.to(self.labels.device)
+        words = (ops.pack_allow_mask(allow) if allow.dtype == torch.bool else allow).contiguous()
+        view = IVFIndex(*(getattr(self, n) for n in self._TENSORS), metric=self.metric, N=self.N)
+        view.row_allow, view.list_allow, view.list_eligible = ops.ivf_mask_lists(
+            words, self.N, self.labels, self.list_begin, self.list_len)
+        view.eligible = view.list_eligible.sum()
+        return view
+
     def state_dict(self) -> Dict[str, object]:
+        if self.row_allow is not None:
+            raise ValueError("a restricted view is not saved: a mask is per request; save the base index")
         d: Dict[str, object] = {n: getattr(self, n) for n in self._TENSORS}
         d["metric"], d["N"] = self.metric, self.N
         return d
@@ -101,10 +137,13 @@ class IVFIndex:
 
     def probes(self, user_emb: torch.Tensor, nprobe: int) -> torch.Tensor:
         """The coarse step: int32 [M, min(nprobe, L)], each query's nearest centroids (by L2 for
-        metric "l2", by inner product for "dot")."""
+        metric "l2", by inner product for "dot"). On a restricted view only lists that hold an
+        eligible item count (the exact filtered kernel with ``list_allow`` as the item mask); where
+        fewer than nprobe such lists exist the tail columns are -1, which the scan takes for "no
+        probe"."""
         nprobe = max(1, min(int(nprobe), self.nlist))
         ids, _ = ops.topk_mips(user_emb, self.centroids, nprobe,
-                               bias=self.centroid_bias if self.metric == "l2" else None)
+                               bias=self.centroid_bias if self.metric == "l2" else None, allow=self.list_allow)
         return ids.to(torch.int32)
 
     def search(self, user_emb: torch.Tensor, k: int, nprobe: int,
@@ -113,7 +152,8 @@ class IVFIndex:
         """(ids [M, k] int64 item row indices, -1 where fewer than k are left; scores [M, k] fp32):
         the top ``k`` of each query over its ``nprobe`` nearest lists (at most 64, clamped to L).
         ``seen``: (values int32 [S] item rows, ascending per query as ops.sort_exclusions leaves
-        them, offsets int64 [M + 1]), never returned to that query."""
+        them, offsets int64 [M + 1]), never returned to that query. On a restricted view, over the
+        eligible items only."""
         M = user_emb.shape[0]
         ids = torch.empty(M, k, dtype=torch.int64, device=user_emb.device)
         scores = torch.empty(M, k, dtype=torch.float32, device=user_emb.device)
@@ -122,7 +162,7 @@ class IVFIndex:
             q = user_emb[lo:lo + n]
             exclude = None if seen is None else (seen[0], seen[1][lo:lo + n + 1])
             i, s = ops.ivf_scan(q, self.rows, self.labels, self.list_begin, self.list_len, self.probes(q, nprobe), k,
-                                bias=self.bias, exclude=exclude)
+                                bias=self.bias, exclude=exclude, row_allow=self.row_allow)
             ids[lo:lo + n] = i
             scores[lo:lo + n] = s
         return ids, scores

@@ -216,12 +216,16 @@ def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metri
     ``index`` (ivf.IVFIndex over the same ``item_emb``, built for the same ``metric``): the
     approximate query instead, each user against its ``nprobe`` nearest lists only
     (IVFIndex.search); ids, scores and the seen lists as above, ``item_emb`` and ``bias`` are not
-    read (the index holds its own copy), ``allow`` is not supported."""
+    read (the index holds its own copy). An item mask goes to the index itself, as the reference's
+    ``filters=`` does: pass ``index=index.restricted(allow)`` (the coarse step then counts only lists
+    with an eligible item, the fine step is the masked list scan); ``allow=`` beside ``index=`` is
+    refused."""
     if metric not in ("dot", "l2"):
         raise ValueError("metric must be 'dot' or 'l2'")
     if index is not None:
         if allow is not None:
-            raise ValueError("allow masks are not supported with an index")
+            raise ValueError("allow masks are not supported with an index: pass index=index.restricted(allow) "
+                             "(IVFIndex.restricted)")
         if index.metric != metric:
             raise ValueError(f"the index was built for metric {index.metric!r}, not {metric!r}")
         _, seen = _retrieval_filters(index.N, user_emb.shape[0], user_emb.device, None, seen_values, seen_offsets)
@@ -253,7 +257,7 @@ def retrieve_fused(step, user_rows: torch.Tensor, k: int = 100, metric: str = "d
     through the query tower (as export does), against the item table through the candidate tower
     (export_fused, unless its embeddings ``item_emb`` are passed in). ``allow``, ``seen_values`` /
     ``seen_offsets``, ``query_chunk``, ``index`` and ``nprobe`` as retrieve() (with an index the
-    item tower is not run)."""
+    item tower is not run; an item mask with an index is ``index=index.restricted(allow)``)."""
     towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
     x = step.tables.table_view(0)[user_rows.to(step.device)]
     for w, b in towers[0]:
@@ -275,7 +279,8 @@ def evaluate_retrieval(step, user_rows: torch.Tensor, target_values: torch.Tenso
     metrics.retrieval_metrics' dict. ``allow`` and ``seen_values`` / ``seen_offsets`` as retrieve():
     with each user's training positives as the seen set, the held-out items are ranked among the
     items the user has not seen, which is the usual protocol. ``index`` / ``nprobe`` as retrieve():
-    the approximate query (ivf.IVFIndex) in place of the exact one."""
+    the approximate query (ivf.IVFIndex, or its restricted(allow) view for an item mask) in place of
+    the exact one."""
     from .metrics import retrieval_metrics
 
     ids, _ = retrieve_fused(step, user_rows, k=k, metric=metric, item_emb=item_emb, allow=allow,

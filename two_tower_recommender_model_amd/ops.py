@@ -966,15 +966,20 @@ def topk_mips(queries: torch.Tensor, items: torch.Tensor, k: int, bias: Optional
 
 def ivf_scan(queries: torch.Tensor, rows: torch.Tensor, labels: torch.Tensor, list_begin: torch.Tensor,
              list_len: torch.Tensor, probes: torch.Tensor, k: int, bias: Optional[torch.Tensor] = None,
-             exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+             exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+             row_allow: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """The fine step of an IVF index (tt_ivf_scan): for each row of ``queries`` [M, E] the top ``k`` of
     the items in the lists ``probes`` [M, nprobe] (int32, distinct within a row; a value outside
     [0, L) is no probe) names. ``rows`` [P, E] bf16 are the item rows in list order, ``bias`` [P]
     fp32 / ``labels`` [P] int32 (original item index) in the same order, list l = rows
     [list_begin[l], list_begin[l] + list_len[l]) (int64 [L], int32 [L]). ``exclude`` as topk_mips,
     in original item indices. Returns (ids [M, k] int64 original item indices, -1 where fewer than k
-    are left; scores [M, k] fp32): exactly topk_mips over the probed lists' items, bit for bit."""
-    _dev(queries, rows, labels, list_begin, list_len, probes, bias)
+    are left; scores [M, k] fp32): exactly topk_mips over the probed lists' items, bit for bit.
+
+    ``row_allow`` (ivf_mask_lists: int32 [ceil(P / 32)], a bit per packed row) restricts every query
+    to the eligible rows (tt_ivf_scan_masked): exactly topk_mips with the item mask it was made from,
+    over the probed lists' items. None is the unmasked call."""
+    _dev(queries, rows, labels, list_begin, list_len, probes, bias, row_allow)
     if exclude is not None:
         _dev(*exclude)
     if queries.dim() != 2 or rows.dim() != 2 or queries.shape[1] != rows.shape[1] or queries.stride(1) != 1:
@@ -1007,11 +1012,49 @@ def ivf_scan(queries: torch.Tensor, rows: torch.Tensor, labels: torch.Tensor, li
     lib = _lib_()
     ids = torch.empty(M, k, dtype=torch.int64, device=dev)
     scores = torch.empty(M, k, dtype=torch.float32, device=dev)
+    if row_allow is not None and (row_allow.dtype != torch.int32 or row_allow.dim() != 1 or
+                                  row_allow.numel() != (P + 31) // 32 or not row_allow.is_contiguous()):
+        raise _lib.TTError("ivf_scan: row_allow must be contiguous int32 [ceil(P / 32)] (ivf_mask_lists)")
     ws = scratch(lib.tt_ivf_scan_workspace_bytes(M, nprobe, k, L), dev, "ivf_scan")
-    check(lib.tt_ivf_scan(ptr(queries), _x_code(queries), queries.stride(0), M, E, ptr(rows), ptr(bias), ptr(labels), P,
-                          ptr(list_begin), ptr(list_len), L, ptr(probes), nprobe, ptr(xv), ptr(xo), k, ptr(ids),
-                          ptr(scores), ptr(ws), ws.numel(), stream_handle(dev)), "ivf_scan")
+    if row_allow is None:
+        check(lib.tt_ivf_scan(ptr(queries), _x_code(queries), queries.stride(0), M, E, ptr(rows), ptr(bias), ptr(labels),
+                              P, ptr(list_begin), ptr(list_len), L, ptr(probes), nprobe, ptr(xv), ptr(xo), k, ptr(ids),
+                              ptr(scores), ptr(ws), ws.numel(), stream_handle(dev)), "ivf_scan")
+    else:
+        check(lib.tt_ivf_scan_masked(ptr(queries), _x_code(queries), queries.stride(0), M, E, ptr(rows), ptr(bias),
+                                     ptr(labels), P, ptr(list_begin), ptr(list_len), L, ptr(probes), nprobe, ptr(xv),
+                                     ptr(xo), ptr(row_allow), k, ptr(ids), ptr(scores), ptr(ws), ws.numel(),
+                                     stream_handle(dev)), "ivf_scan_masked")
     return ids, scores
+
+
+def ivf_mask_lists(allow_words: torch.Tensor, N: int, labels: torch.Tensor, list_begin: torch.Tensor,
+                   list_len: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """An item mask in an IVF index's list order (tt_ivf_mask_lists): ``allow_words`` is
+    pack_allow_mask's int32 [ceil(N / 32)] over the original item indices, ``labels`` int32 [P],
+    ``list_begin`` int64 [L] and ``list_len`` int32 [L] the index's. Returns (row_allow int32
+    [ceil(P / 32)]: a bit per packed row, zero on padding; list_allow int32 [ceil(L / 32)]: a bit per
+    list that holds an eligible row; list_eligible int32 [L]: the eligible rows of each list). No
+    host sync; the same inputs give the same bits."""
+    _dev(allow_words, labels, list_begin, list_len)
+    N = int(N)
+    if allow_words.dtype != torch.int32 or allow_words.dim() != 1 or allow_words.numel() != (N + 31) // 32 or \
+            not allow_words.is_contiguous():
+        raise _lib.TTError("ivf_mask_lists: allow_words must be contiguous int32 [ceil(N / 32)] (pack_allow_mask)")
+    if labels.dtype != torch.int32 or labels.dim() != 1 or not labels.is_contiguous():
+        raise _lib.TTError("ivf_mask_lists: labels must be contiguous int32 [P]")
+    P, L = labels.numel(), list_begin.numel()
+    if list_begin.dtype != torch.int64 or list_begin.dim() != 1 or not list_begin.is_contiguous() or \
+            list_len.dtype != torch.int32 or list_len.dim() != 1 or list_len.numel() != L or not list_len.is_contiguous():
+        raise _lib.TTError("ivf_mask_lists: list_begin must be contiguous int64 [L] and list_len int32 [L]")
+    dev = labels.device
+    row_allow = torch.empty((P + 31) // 32, dtype=torch.int32, device=dev)
+    list_allow = torch.empty((L + 31) // 32, dtype=torch.int32, device=dev)
+    list_eligible = torch.empty(L, dtype=torch.int32, device=dev)
+    check(_lib_().tt_ivf_mask_lists(ptr(allow_words), N, ptr(labels), P, ptr(list_begin), ptr(list_len), L,
+                                    ptr(row_allow), ptr(list_allow), ptr(list_eligible), stream_handle(dev)),
+          "ivf_mask_lists")
+    return row_allow, list_allow, list_eligible
 
 
 def ivf_segment_mean(rows: torch.Tensor, order: torch.Tensor, seg_offsets: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
