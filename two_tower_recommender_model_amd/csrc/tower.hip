@@ -2055,8 +2055,12 @@ constexpr int T2_STR = T2_MB + 8;                      // bf16 LDS row stride (8
 constexpr int T2_ROWS = T2_NT + MAXW;                  // Z rows [0, 64) + A rows [64, 64 + K)
 constexpr int T2_LDS = 2 * T2_ROWS * T2_STR * 2;       // bytes (30,720)
 constexpr int T2_RED = 3 * 64 * 16 * 4;                // bytes of the register-path reduction
+constexpr int T2R_STR = 208;                           // bf16 per LDS row of a row-major chunk (416 B)
+constexpr int T2R_RING = 3;                            // chunk buffers of the row-major full-pass ring
+constexpr int T2R_LDS = T2R_RING * TR * T2R_STR * 2;   // bytes (39,936)
 constexpr int T2_SMEM0 = T2_LDS > T2_RED ? T2_LDS : T2_RED;
-constexpr int T2_SMEM = T2_SMEM0 > DD_SMEM ? T2_SMEM0 : DD_SMEM;  // the combined launch shares it with dedup.h
+constexpr int T2_SMEM1 = T2_SMEM0 > T2R_LDS ? T2_SMEM0 : T2R_LDS;
+constexpr int T2_SMEM = T2_SMEM1 > DD_SMEM ? T2_SMEM1 : DD_SMEM;  // the combined launch shares it with dedup.h
 
 
 __device__ __forceinline__ void wgrad_lds_block(const WgradArgs& a, int lb, char* smem) {
@@ -2151,9 +2155,13 @@ __device__ __forceinline__ void wgrad_lds_block(const WgradArgs& a, int lb, char
 // (whole 16-B pieces of rows, three loads per thread as in wgrad_lds_block), and the fragments are
 // transposed reads (ds_read_b64_tr_b16). K-slot (q, j) of every fragment is chunk row
 // 4 q + (j & 3) + 16 (j >> 2): the 32 lanes of a read then address 8 consecutive rows, which the
-// 416-B stride (= 160 mod 256) spreads over all 64 banks
-constexpr int T2R_STR = 208;  // bf16 per LDS row
-static_assert(2 * TR * T2R_STR * 2 <= T2_SMEM, "the row-major staged chunks fit the tail's LDS");
+// 416-B stride (= 160 mod 256) spreads over all 64 banks.
+// The first pass of a slice, when it holds all 256 rows of a full tile, runs t2r_full_pass (pipelined
+// over a ring of T2R_RING chunk buffers, no predicate); every other pass runs the general loop in
+// wgrad_lds_block_rm (two buffers, a chunk at a time, rows and features predicated). Later passes of
+// a slice of more than 256 rows stay on the general loop: pipelined, their accumulators live across
+// the pass loop beside the 24 loads and two fragment sets do not fit the tail's 168 registers
+static_assert(T2R_LDS <= T2_SMEM, "the row-major staged chunks fit the tail's LDS");
 __device__ __forceinline__ bf16x8 t2r_frag(const __bf16* d, int col0, int lane) {
   const int q = lane >> 4, qq = (lane >> 2) & 3, p = lane & 3;
   const __bf16* base = d + (4 * q + qq) * T2R_STR + col0 + 4 * p;
@@ -2161,9 +2169,74 @@ __device__ __forceinline__ bf16x8 t2r_frag(const __bf16* d, int col0, int lane) 
   const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(base + 16 * T2R_STR));
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
+// The FIRST pass of a slice in wgrad_lds_block_rm when it is full: all T2_PF chunks inside the slice and every piece inside the
+// tile (NT = 64, K = 64 or 128), so nothing is zeroed and nothing is predicated: no MFMA behind an
+// exec-mask branch. Chunk c lives in ring buffer c % T2R_RING. Iteration c issues chunk c + 1's
+// fragment reads and chunk c + 2's LDS writes in among chunk c's MFMAs (the sched_group_barriers
+// pin that interleave), then the chunk's one barrier: the reads of chunk c + 1 were issued a whole
+// MFMA group before they are waited for, and the MFMAs of chunk c are in flight at the barrier.
+// Buffer (c + 2) % 3 was last read for chunk c - 1, by reads every wave completed before the
+// barrier of iteration c - 1. `more` (another pass follows, which restarts at buffers 0 and 1 =
+// chunks 6 and 7 here) keeps the barrier behind chunk 6's MFMAs; the last pass drops it.
+// Every accumulator takes the MFMAs of the general loop, same operands, same chunk order.
+// ACT = false: a wave whose 64 dW columns lie past K (kh = 1 at K = 64) stages and joins the
+// barriers only. Chunk 0 accumulates onto a literal zero: acc need not be set by the caller (32
+// zeroed registers would otherwise live beside the 24 loads in flight).
+// The sched_barriers keep the MFMAs, which are free to cross an s_barrier, in their own chunk.
+template <bool ACT>
+__device__ __forceinline__ void t2r_full_pass(const WgradArgs& a, bool more, const bf16x8 (&ld)[T2_PF][3],
+                                              __bf16* buf, int lw0, int lw1, int lw2, int nh, int kh, int lane,
+                                              f32x4 (&acc)[2][4]) {
+  auto stage = [&](int c) {
+    __bf16* d = buf + (c % T2R_RING) * TR * T2R_STR;
+    *reinterpret_cast<bf16x8*>(d + lw0) = ld[c][0];
+    *reinterpret_cast<bf16x8*>(d + lw1) = ld[c][1];
+    *reinterpret_cast<bf16x8*>(d + lw2) = ld[c][2];
+  };
+  auto frags = [&](int c, bf16x8 (&f)[6]) {
+    const __bf16* d = buf + (c % T2R_RING) * TR * T2R_STR;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) f[i] = t2r_frag(d, nh * 32 + i * 16, lane);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[2 + j] = t2r_frag(d, T2_NT + kh * 64 + j * 16, lane);
+  };
+  bf16x8 f[2][6];
+  stage(0);
+  stage(1);
+  __syncthreads();
+  T2_STAMP(1);
+  if (ACT) frags(0, f[0]);
+#pragma unroll
+  for (int c = 0; c < T2_PF; ++c) {
+    __builtin_amdgcn_sched_barrier(0);
+    if (c + 2 < T2_PF) stage(c + 2);
+    if (ACT && c + 1 < T2_PF) frags(c + 1, f[(c + 1) & 1]);
+    if (ACT) {
+      // j outside i: a B fragment is dead after its two MFMAs, the next chunk's reuses its registers
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[c & 1][i], f[c & 1][2 + j],
+                                                              c == 0 ? (f32x4)(0.f) : acc[i][j], 0, 0, 0);
+      if (c + 1 < T2_PF) {
+        if (c + 2 < T2_PF) __builtin_amdgcn_sched_group_barrier(0x200, 3, 0);  // the 3 DS writes
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);  // 1 MFMA
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // 2 DS reads: one fragment
+        }
+        __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (c + 2 < T2_PF || (c + 2 == T2_PF && more)) __syncthreads();
+  }
+}
 __device__ __forceinline__ void wgrad_lds_block_rm(const WgradArgs& a, int lb, char* smem) {
   __bf16* buf = reinterpret_cast<__bf16*>(smem);
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r = lane & 15, q = lane >> 4;
   const int s = __builtin_amdgcn_readfirstlane(lb / a.ntiles), ti = __builtin_amdgcn_readfirstlane(lb % a.ntiles);
   T2_STAMP(0);
@@ -2194,11 +2267,45 @@ __device__ __forceinline__ void wgrad_lds_block_rm(const WgradArgs& a, int lb, c
   const int lw2 = prow2 * T2R_STR + T2_NT + 8 * ((tid + 256) & 15);
   const int nh = wid >> 1, kh = wid & 1;  // wave: dW rows [32 nh, +32) x columns [64 kh, +64)
   f32x4 acc[2][4];
+  auto zero_acc = [&]() {
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4)(0.f);
-  for (int64_t p0 = mb; p0 < me; p0 += T2_PF * T2_MB) {
+      for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4)(0.f);
+  };
+  // full tile (wave-uniform, from scalar kernel arguments): every piece of every thread is inside it
+  const bool full_tile = NT == T2_NT && (K == 64 || K == MAXW);
+  constexpr int64_t PASS = T2_PF * T2_MB;
+  // the loads of a full pass of a full tile (the pipelined, branch-free loop takes them). A piece
+  // past K (the upper half of a row at K = 64) rereads the slice's first row, as in the general
+  // loop; it lands in LDS columns that only the idle waves' fragments would cover
+  auto full_loads = [&](int64_t p0, bf16x8 (&ld)[T2_PF][3]) {
+    const uint32_t dr = (uint32_t)(p0 - mb);
+#pragma unroll
+    for (int c = 0; c < T2_PF; ++c) {
+      const uint32_t rc = dr + c * T2_MB;
+      ld[c][0] = *reinterpret_cast<const bf16x8*>(zb + zo + rc * zstr);
+      ld[c][1] = *reinterpret_cast<const bf16x8*>(ab + ao1 + (ok1 ? rc * astr : 0u));
+      ld[c][2] = *reinterpret_cast<const bf16x8*>(ab + ao2 + (ok2 ? rc * astr : 0u));
+    }
+  };
+  int64_t p0 = mb;
+  if (full_tile && mb + PASS <= me) {  // the first pass is full (at the north star: the only pass)
+    bf16x8 ld[T2_PF][3];
+    full_loads(p0, ld);
+    T2_STAMP(4);  // operand loads issued
+    const bool more = mb + PASS < me;
+    if (kh * 64 < K) {
+      t2r_full_pass<true>(a, more, ld, buf, lw0, lw1, lw2, nh, kh, lane, acc);
+    } else {
+      zero_acc();
+      t2r_full_pass<false>(a, more, ld, buf, lw0, lw1, lw2, nh, kh, lane, acc);
+    }
+    p0 += PASS;
+  } else {
+    zero_acc();
+  }
+  for (; p0 < me; p0 += PASS) {
     bf16x8 ld[T2_PF][3];
     const uint32_t dr = (uint32_t)(p0 - mb);  // rows into the slice
     // every load unconditional (an invalid piece reads the slice's first row and is zeroed after):
@@ -2216,6 +2323,7 @@ __device__ __forceinline__ void wgrad_lds_block_rm(const WgradArgs& a, int lb, c
       ld[c][1] = *reinterpret_cast<const bf16x8*>(ab + ao1 + (okc[c][1] ? rc * astr : 0u));
       ld[c][2] = *reinterpret_cast<const bf16x8*>(ab + ao2 + (okc[c][2] ? rc * astr : 0u));
     }
+    if (p0 == mb) T2_STAMP(4);  // operand loads issued
 #pragma unroll
     for (int c = 0; c < T2_PF; ++c) {
       if (p0 + c * T2_MB >= me) break;  // uniform: the slice's tail
