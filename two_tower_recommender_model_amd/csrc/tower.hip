@@ -1431,20 +1431,34 @@ __device__ __forceinline__ float rk_label(RkRaw r, int dt) {
 // ---------------------------------------------------------------------------------------------
 // T3: reduce + Adam + bf16 weight copies
 
-struct UpdateArgs {
+// One segment of the flat parameter vector, W or b of (t, l), is a 16-B record, so the table is four
+// 64-B lines that t3_seg fetches two at a time (every offset is far below 2^31: the shape limits
+// bound P at 2 (1024 x 128 + 3 x 128 x 128 + 4 x 128)). A vector type: the records are pinned in
+// SGPRs, four registers each.
+//   .x  first element in params (INT32_MAX: unused record, never selected)
+//   .y  W: element offset in the bf16 copies
+//   .z  n | k << 16 (b: k = 1)
+//   .w  isw | t << 1 | l << 2
+typedef uint32_t t3_u32x4 __attribute__((ext_vector_type(4)));
+constexpr int T3_NSEG = 2 * 2 * MAXL;
+
+struct alignas(64) UpdateArgs {
+  // line 0: all that stands in front of update_block's first slab, parameter and moment loads
   float* params;
   float* exp_avg;
   float* exp_avg_sq;
   const float* slab;
-  const float* dbpart;
-  int64_t P;
+  const float* adam_pre;  // nullable: step size / sqrt(bias correction 2) precomputed by T2 (which
+                          // also advanced step_state): no pow() and no arrival ticket here
+  const float* grads_in;  // nullable: take the gradient from here (data-parallel: all-reduced)
+  int32_t P;
   int S;
-  int nwg;
+  int do_adam;
   int nseg;
-  // segments of the flat parameter vector: W or b of (t, l)
-  int64_t seg_off[2 * 2 * MAXL + 1];
-  int32_t seg_t[2 * 2 * MAXL], seg_l[2 * 2 * MAXL], seg_isw[2 * 2 * MAXL], seg_n[2 * 2 * MAXL], seg_k[2 * 2 * MAXL];
-  int64_t seg_wc[2 * 2 * MAXL];  // bf16 copy offset for W segments
+  // lines 1..4: the segment table, ascending offsets; two layers' eight records are lines 1..2
+  t3_u32x4 seg[T3_NSEG];
+  const float* dbpart;
+  int nwg;
   __bf16* wb;
   __bf16* wtb;
   __bf16* wbf;
@@ -1452,11 +1466,7 @@ struct UpdateArgs {
   int skip_plain;  // wb / wtb unused by this shape's T1 (tower_l2_kernel): not written
   float lr, beta1, beta2, eps, wd;
   int64_t* step_state;
-  int do_adam;
   float* grads_out;  // nullable: the reduced gradient (tests / inspection)
-  const float* grads_in;  // nullable: take the gradient from here (data-parallel: all-reduced)
-  const float* adam_pre;  // nullable: step size / sqrt(bias correction 2) precomputed by T2 (which
-                          // also advanced step_state): no pow() and no arrival ticket here
   // data-parallel towers without an all-reduce launch (pipelined sharded step): grads_out is
   // written out_copies times (stride out_stride, scaled by out_scale: one copy per destination
   // rank of the exchange), and grads_in is the fixed-order sum of in_srcs vectors (stride in_stride)
@@ -1472,6 +1482,13 @@ struct UpdateArgs {
   int64_t* stamps;  // EXPERIMENT (TT_RING_STAMPS): [workgroups][4] s_memrealtime per phase
 #endif
 };
+// T3's workgroup size: every launch of update_block is 256 wide (a constant, so that no load of the
+// launch dimensions stands in front of the slab loads); the experiment build also tries 128
+#if TT_EXPERIMENTS
+#define T3_BLOCK ((int)blockDim.x)
+#else
+#define T3_BLOCK 256
+#endif
 #if TT_EXPERIMENTS
 #define T3_STAMP(k) \
   do { if (a.stamps && threadIdx.x == 0 && bid < 512) a.stamps[(int64_t)bid * 4 + (k)] = (int64_t)__builtin_amdgcn_s_memrealtime(); } while (0)
@@ -1479,27 +1496,47 @@ struct UpdateArgs {
 #define T3_STAMP(k) do { } while (0)
 #endif
 
-// one parameter's segment (W or b of tower t, layer l): a loop over the (wave-uniform) segment list
-// with scalar kernarg loads and per-lane selects — a per-lane index into the kernarg arrays would be
-// a chain of dependent vector loads from the kernarg segment (several us per launch)
+// one parameter's segment (W or b of tower t, layer l): per-lane compares and selects over the
+// table held in SGPRs — no load and no branch per segment. update_block calls this behind its slab
+// loads, which need no segment. A per-lane index into the kernarg table would be a chain of
+// dependent vector loads from the kernarg segment (several us per launch); a scalar load per
+// segment inside `if (i >= off[q])` was about twenty serial scalar round trips in front of the
+// slab loads.
 struct T3Seg {
   int64_t soff = 0, swc = 0;
   int sisw = 0, sk = 1, sn = 1, st_ = 0, sl_ = 0;
 };
-__device__ __forceinline__ T3Seg t3_seg(const UpdateArgs& a, int64_t i) {
-  T3Seg g;
+__device__ __forceinline__ T3Seg t3_seg(const UpdateArgs& a, int64_t i, int nseg) {
+  // the last record at or below i wins (ascending offsets); unused records hold INT32_MAX (i < P)
+  const int32_t ii = (int32_t)i;
+  int32_t off = 0, wc = 0;
+  uint32_t nk = 1u | 1u << 16, meta = 0;
+  // eight records (two 64-B lines) at a time: their scalar loads issued together, one wait (the
+  // empty asm holds all eight in SGPRs at once; left alone they load and wait line by line)
+  const auto half = [&](int q0) {
+    t3_u32x4 r[8];
 #pragma unroll
-  for (int q = 0; q < 2 * 2 * MAXL; ++q) {
-    if (q < a.nseg && i >= a.seg_off[q]) {
-      g.soff = a.seg_off[q];
-      g.sisw = a.seg_isw[q];
-      g.sk = a.seg_k[q];
-      g.sn = a.seg_n[q];
-      g.swc = a.seg_wc[q];
-      g.st_ = a.seg_t[q];
-      g.sl_ = a.seg_l[q];
+    for (int q = 0; q < 8; ++q) r[q] = a.seg[q0 + q];
+    asm volatile("" ::"s"(r[0]), "s"(r[1]), "s"(r[2]), "s"(r[3]), "s"(r[4]), "s"(r[5]), "s"(r[6]), "s"(r[7]));
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const bool c = ii >= (int32_t)r[q].x;
+      off = c ? (int32_t)r[q].x : off;
+      wc = c ? (int32_t)r[q].y : wc;
+      nk = c ? r[q].z : nk;
+      meta = c ? r[q].w : meta;
     }
-  }
+  };
+  half(0);
+  if (nseg > 8) half(8);  // three or four layers
+  T3Seg g;
+  g.soff = off;
+  g.swc = wc;
+  g.sisw = (int)(meta & 1u);
+  g.st_ = (int)(meta >> 1 & 1u);
+  g.sl_ = (int)(meta >> 2);
+  g.sn = (int)(nk & 0xffffu);
+  g.sk = (int)(nk >> 16);
   return g;
 }
 
@@ -2663,57 +2700,101 @@ __global__ void __launch_bounds__(256, 3) tower_wgrad_route_rowwise_kernel(Wgrad
   }
 }
 
-__device__ __forceinline__ void update_block(const UpdateArgs& a, int bid, int nblocks) {
+// REMAP: the parameter blocks a contiguous 1/8 per XCD (xcd_remap of workgroup b of nblocks)
+template <bool REMAP = false>
+__device__ __forceinline__ void update_block(const UpdateArgs& a, int b, int nblocks) {
+  // The entry batch: every scalar in front of the first slab load (UpdateArgs' line 0, the wait
+  // flag, the launch dimensions), one group of scalar loads with one wait. The empty asm pins them
+  // in SGPRs and, as its outputs, keeps every use below it: a use scheduled between two of the
+  // loads costs a wait of its own (scalar loads return out of order, so any wait is for all), and
+  // left alone the compiler sinks each load into the branch that uses it, a serial round trip each.
+  const float* params = a.params;
+  const float* exp_avg = a.exp_avg;
+  const float* exp_avg_sq = a.exp_avg_sq;
+  const float* slab = a.slab;
+  const float* adam_pre = a.adam_pre;
+  const float* grads_in = a.grads_in;
+  const float* grads_out = a.grads_out;
+  int64_t P = a.P;
+  int S = a.S, do_adam = a.do_adam, nseg = a.nseg, wt_w = a.wt.W;
+  asm volatile(""
+               : "+s"(P), "+s"(S), "+s"(do_adam), "+s"(nseg), "+s"(wt_w), "+s"(nblocks)
+               : "s"(slab), "s"(adam_pre), "s"(grads_in), "s"(params), "s"(exp_avg), "s"(exp_avg_sq), "s"(grads_out));
+  const int bid = REMAP ? xcd_remap(b, nblocks) : b;
   T3_STAMP(0);
-  if (a.wt.W) {
+  if (wt_w) {
     if (bid == 0) px_signal(a.wt);
     px_wait(a.wt);
   }
-  const int64_t i = (int64_t)bid * blockDim.x + threadIdx.x;
+  const int64_t i = (int64_t)bid * T3_BLOCK + threadIdx.x;
   int64_t t_step = 0;
   float step_size = 0.f, bc2_sqrt = 1.f;
-  if (a.do_adam && a.adam_pre) {
-    step_size = a.adam_pre[0];
-    bc2_sqrt = a.adam_pre[1];
-  } else if (a.do_adam) {
+  // (T2's precomputed Adam scalars are loaded below, behind the slab loads: in front of them the
+  // slab loads would wait out that load's latency first)
+  const bool pre = do_adam && adam_pre;
+  if (do_adam && !pre) {
     t_step = a.step_state[0] + 1;
     const double bc1 = 1.0 - pow((double)a.beta1, (double)t_step);
     const double bc2 = 1.0 - pow((double)a.beta2, (double)t_step);
     step_size = (float)((double)a.lr / bc1);
     bc2_sqrt = (float)sqrt(bc2);
   }
-  if (i < a.P) {
-    const T3Seg sg = t3_seg(a, i);
-    const float p = a.params[i];
-    const float m = a.do_adam ? a.exp_avg[i] : 0.f, v = a.do_adam ? a.exp_avg_sq[i] : 0.f;
-    float g = 0.f;
-    if (a.grads_in) {
-      g = a.grads_in[i];
-      for (int q = 1; q < a.in_srcs; ++q) g += a.grads_in[(int64_t)q * a.in_stride + i];
-    } else if (a.do_adam || a.grads_out) {
-      if (sg.sisw) {
-        // a round's 32 slab loads all in flight (one memory latency per 32 slabs, not per load);
-        // the sum keeps the sequential order s = 0, 1, ...
-        for (int s0 = 0; s0 < a.S; s0 += 32) {
-          float v[32];
+  if (i < P) {
+    // a round's 32 slab loads all in flight (one memory latency per 32 slabs, not per load); the
+    // sum keeps the sequential order s = 0, 1, ... A round is one basic block: the loads past S - 1
+    // read slab S - 1 again (the same cache line) and their values are not added, where a branch
+    // per load would end the block and put a wait for every earlier load at the join.
+    float sv[32];
+    const auto slab_issue = [&](int s0) {
 #pragma unroll
-          for (int u = 0; u < 32; ++u) {
-            v[u] = s0 + u < a.S ? a.slab[(int64_t)(s0 + u) * a.P + i] : 0.f;
-          }
+      for (int u = 0; u < 32; ++u)  // S P < 2^31: a scalar base per slab, the lane's offset shared by all
+        sv[u] = (slab + (uint32_t)(s0 + u < S ? s0 + u : S - 1) * (uint32_t)P)[(uint32_t)i];
+    };
+    const auto slab_sum = [&](int s0, float g) {
 #pragma unroll
-          for (int u = 0; u < 32; ++u)
-            if (s0 + u < a.S) g += v[u];
-        }
-      } else {
-        // bias gradient, reduced over the T1 workgroups by T2's bias waves
-        g = a.slab[i];
+      for (int u = 0; u < 32; ++u) g = s0 + u < S ? g + sv[u] : g;
+      return g;
+    };
+    // the moments' addresses without a branch (no Adam: the parameter again, value unused)
+    const float* const mp = do_adam ? exp_avg : params;
+    const float* const vp = do_adam ? exp_avg_sq : params;
+    // and Adam's scalars' (no precomputed pair: the first two parameters, values unused)
+    const float* const sp = pre ? adam_pre : params;
+    float g = 0.f, p, m, v, pre0, pre1;
+    const auto state_issue = [&]() { p = params[i], m = mp[i], v = vp[i], pre0 = sp[0], pre1 = sp[1]; };
+    T3Seg sg;
+    if (!grads_in && (do_adam || grads_out)) {
+      // The first round's loads wait for nothing but the entry batch. A bias element (its gradient
+      // is slab 0's alone, reduced over the T1 workgroups by T2's bias waves) issues the same loads
+      // and keeps the first, so which segment a lane is in is not needed yet: the segment table's
+      // scalar loads and the select run while the slab, parameter and moment loads are in flight.
+      slab_issue(0);
+      state_issue();
+      sg = t3_seg(a, i, nseg);
+      // (the select stands in front of the sum: the first addend passes through the asm with it)
+      asm volatile("" : "+v"(sv[0]) : "v"(sg.soff), "v"(sg.swc), "v"(sg.sisw), "v"(sg.sk), "v"(sg.sn), "v"(sg.st_), "v"(sg.sl_));
+      const float gb = sv[0];
+      g = slab_sum(0, g);
+      for (int s0 = 32; s0 < S; s0 += 32) {
+        slab_issue(s0);
+        g = slab_sum(s0, g);
       }
+      g = sg.sisw ? g : gb;
+    } else {
+      if (grads_in) {
+        g = grads_in[i];
+        for (int q = 1; q < a.in_srcs; ++q) g += grads_in[(int64_t)q * a.in_stride + i];
+      }
+      state_issue();
+      sg = t3_seg(a, i, nseg);
     }
+    if (!do_adam) m = 0.f, v = 0.f;
+    if (pre) step_size = pre0, bc2_sqrt = pre1;
     T3_STAMP(1);
-    t3_apply(a, i, sg, p, m, v, g, step_size, bc2_sqrt, a.do_adam);
+    t3_apply(a, i, sg, p, m, v, g, step_size, bc2_sqrt, do_adam);
     T3_STAMP(2);
   }
-  if (a.do_adam && !a.adam_pre) {
+  if (do_adam && !pre) {
     __syncthreads();
     if (threadIdx.x == 0) {
       unsigned* counter = reinterpret_cast<unsigned*>(a.step_state + 1);
@@ -2731,7 +2812,7 @@ __device__ __forceinline__ void update_block(const UpdateArgs& a, int bid, int n
 // of its workgroup): -0.45 us a step at the north star against blockIdx order, same box
 // (profiles/r06y2_ab_t3_by_xcd.log)
 __global__ void __launch_bounds__(256) tower_update_kernel(UpdateArgs a) {
-  update_block(a, xcd_remap((int)blockIdx.x, (int)gridDim.x), (int)gridDim.x);
+  update_block<true>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // Pipelined sharded step, launch G (after launch U updated this rank's rows): the owner's gather of
@@ -2746,7 +2827,7 @@ __global__ void __launch_bounds__(256) tower_grads_place_gather_kernel(UpdateArg
   if (g.epoch && b == 0 && threadIdx.x == 0)  // exchange B's epoch advances with its producer
     __hip_atomic_fetch_add(g.epoch, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (b < n_upd) {
-    update_block(a, xcd_remap(b, n_upd), n_upd);  // a contiguous 1/8 per XCD, as T3
+    update_block<true>(a, b, n_upd);  // a contiguous 1/8 per XCD, as T3
   } else if (b < n_upd + n_place) {
     const int j = b - n_upd;
     route_place_block<true>(r, j % r.nblk, j / r.nblk, base, wc);
@@ -3492,25 +3573,24 @@ static int t3_args(const tt_tower_shape_t* shape, int64_t B, void* workspace, si
   a.exp_avg_sq = rep ? nullptr : u.exp_avg_sq;
   a.slab = reinterpret_cast<const float*>(ws + L.o_slab);
   a.dbpart = reinterpret_cast<const float*>(ws + L.o_dbpart);
-  a.P = L.P;
+  a.P = (int32_t)L.P;
   a.S = L.S;
   a.nwg = L.nwg;
+  // the segment records' fields and update_block's 32-bit slab offsets (the shape limits keep far below)
+  if ((int64_t)L.S * L.P >= INT32_MAX / 4 || L.PW >= INT32_MAX)
+    return fail(TT_EINVAL, "tower: parameter vector too long for the segment table");
   int sg = 0;
+  const auto rec = [&](int64_t off, int64_t wc, int n, int k, int isw, int t, int l) {
+    a.seg[sg++] = t3_u32x4{(uint32_t)off, (uint32_t)wc, (uint32_t)n | (uint32_t)k << 16,
+                           (uint32_t)isw | (uint32_t)t << 1 | (uint32_t)l << 2};
+  };
   for (int t = 0; t < 2; ++t)
     for (int l = 0; l < shape->L; ++l) {
-      a.seg_off[sg] = L.woff[t][l];
-      a.seg_t[sg] = t; a.seg_l[sg] = l; a.seg_isw[sg] = 1;
-      a.seg_n[sg] = shape->width[l]; a.seg_k[sg] = L.K[t][l];
-      a.seg_wc[sg] = L.wcoff[t][l];
-      ++sg;
-      a.seg_off[sg] = L.boff[t][l];
-      a.seg_t[sg] = t; a.seg_l[sg] = l; a.seg_isw[sg] = 0;
-      a.seg_n[sg] = shape->width[l]; a.seg_k[sg] = 1;
-      a.seg_wc[sg] = 0;
-      ++sg;
+      rec(L.woff[t][l], L.wcoff[t][l], shape->width[l], L.K[t][l], 1, t, l);
+      rec(L.boff[t][l], 0, shape->width[l], 1, 0, t, l);
     }
   a.nseg = sg;
-  a.seg_off[sg] = L.P;
+  while (sg < T3_NSEG) rec(INT32_MAX, 0, 1, 1, 0, 0, 0);  // never selected
   a.wb = reinterpret_cast<__bf16*>(ws + L.o_wb);
   a.wtb = reinterpret_cast<__bf16*>(ws + L.o_wtb);
   a.wbf = reinterpret_cast<__bf16*>(ws + L.o_wbf);
