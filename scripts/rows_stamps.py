@@ -39,7 +39,7 @@ for it in range(4):
     if it < 3:
         continue
     w = st.towers.ws[off:off + dbg_bytes].view(torch.int64)[8192:8192 + nwg * 16 * 9].view(nwg, 16, 9).cpu().double()
-    extra = w[:, :4, 4:8]
+    extra = w[:, :5, 4:8]
     img = w[:, :4, 8]
     w = w[:, :, :4]
     t0 = w[:, 0, :].min(dim=1, keepdim=True).values
@@ -50,7 +50,10 @@ for it in range(4):
         mx = rel[:, k, :].max(dim=1).values.median()
         print(f"  {k:3d}  " + " ".join(f"{float(x):8.2f}" for x in med) + f"  {float(mx):6.2f}")
     ex = (extra - t0.unsqueeze(1)) / 100.0
-    for k, what in enumerate(["G^2 sums", "step + LDS write-back", "row stores issued", "state / dX stores"]):
+    # (u4: between the id wait and the row-index shuffles; a library without that stamp leaves
+    # whatever the workspace held)
+    for k, what in enumerate(["G^2 sums", "step + LDS write-back", "row stores issued", "state / dX stores",
+                              "ids landed"]):
         print(f"  u{k} {what:24s}" + " ".join(f"{float(x):8.2f}" for x in ex[:, k, :].median(dim=0).values))
     if image_wave:
         im = (img - t0) / 100.0

@@ -47,7 +47,66 @@ __device__ __forceinline__ int64_t strip_at(int64_t f, int64_t m, int64_t nf) {
   return (((m >> 5) * nf + f) << 5) + (m & 31);
 }
 
-struct TowerArgs {
+// The row-owned T1's argument front (tower_rows_body), built by launch_t1 (rk_front): what its
+// compute waves read, laid out by WHEN they read it, so that each phase's scalar loads are one batch
+// of whole 64-B lines of the kernel-argument segment with one wait (as UpdateArgs for T3). A wave
+// reads the common record and its tower's record, selected by one wave-uniform offset: everything
+// per tower (pointers advanced to the tower's block, offsets folded in) is precomputed on the host.
+struct alignas(64) RkTower {
+  // line 0, the entry batch: all that the id, claim, bias and row-DMA addresses need
+  const void* idcol;       // gcol[t]; IDX: gpos[t]
+  const void* tab;         // gtab[t]; IDX: gsrc[t]; POOL: pooled + in_col[t]
+  int64_t gmod;
+  const float* b0;         // params + boff[t][0]
+  const float* b1;         // params + boff[t][1]
+  const int32_t* claim;    // UPD: dd.claim + t B
+  const int32_t* pos_out;  // IDX: gpos_out[t], null: the input row's index
+  int64_t rstride;         // POOL: floats between source rows (ldp)
+  // line 1: the strips and the row's state (the late batch, behind the row DMAs), the dZ strips
+  // and the gradient rows (the update batch, in front of the dZ0 product)
+  __bf16* xt;              // xt + t in_max Bp
+  __bf16* act0;            // act + (t MAXL + 0) MAXW Bp
+  float* us;               // UPD: us[t]
+  __bf16* dzt0;            // dzt + (t MAXL + 0) MAXW Bp
+  __bf16* dzt1;            // dzt + (t MAXL + 1) MAXW Bp
+  float* grow;             // gpooled + in_col[t]; IDX: gdst[t]
+  float* prow;             // pooled_out + in_col[t], null without pooled_out
+  int64_t pad1_;
+  // line 2: the table rows (update batch: it brings the line in), the bias partials (epilogue)
+  float* uw;               // UPD: uw[t]
+  float* db0;              // dbpart + (t MAXL + 0) nwg MAXW
+  float* db1;              // dbpart + (t MAXL + 1) nwg MAXW
+  int64_t pad2_[5];
+};
+struct alignas(64) RkCommon {
+  // line 0: entry (B .. gid_dtype), the late batch (the rest)
+  int64_t B;
+  const void* labels;
+  int32_t label_dtype;
+  int32_t gid_dtype;
+  float grad_scale;
+  int32_t in_max;
+  DSlot* slots;            // UPD: dd.slots
+  int32_t* ctr;            // UPD: dd.ctr
+  float ulr, ueps;
+  int32_t nwg;             // the grid (the tile's XCD placement needs it at entry)
+  float fB;                // (float)B, for the late batch: B itself need not live up to the logit
+  // line 1: the update batch and the epilogue
+  int64_t ldp;
+  int32_t* multi;          // UPD: dd.multi
+  float* logits;
+  float* loss_part;
+  int32_t nseg;            // UPD: dd.nseg
+  int32_t pad1_[7];
+};
+struct RkFront {
+  RkCommon c;
+  RkTower tw[2];
+};
+static_assert(sizeof(RkTower) == 192 && sizeof(RkCommon) == 128, "whole 64-B lines");
+
+struct alignas(64) TowerArgs {
+  RkFront rk;  // first: 64-B aligned in the kernel-argument segment
   tt_tower_shape_t s;
   int64_t B;
   const float* pooled;  // [B, ldp]
@@ -1413,6 +1472,19 @@ __device__ __forceinline__ float rk_label(RkRaw r, int dt) {
   if (dt == TT_I64) return (float)(int64_t)(((uint64_t)r.hi << 32) | r.lo);
   return __uint_as_float(r.lo);
 }
+// N per-lane values (addresses, row indices) pinned in VGPRs at one point: everything they depend
+// on (a batch of shuffles or LDS reads) is issued and waited for once in front of it, where the
+// compiler would otherwise interleave each value's wait with its use
+template <int N, typename T>
+__device__ __forceinline__ void rk_pin(T (&p)[N]) {
+  static_assert(N == 2 || N == 4 || N == 8, "2, 4 or 8 values");
+  if constexpr (N == 8)
+    asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]), "+v"(p[4]), "+v"(p[5]), "+v"(p[6]), "+v"(p[7]));
+  else if constexpr (N == 4)
+    asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3]));
+  else
+    asm volatile("" : "+v"(p[0]), "+v"(p[1]));
+}
 // EXPERIMENT (TT_T1_DEBUG bit 8): lane 0 of each wave at point k: stamps[8192 + (wg * 16 + k) * 9 + wave]
 #if TT_EXPERIMENTS
 #define RK_STAMP(k) \
@@ -1623,34 +1695,55 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     return;
   }
   const int t = wid >> 1, h = wid & 1, q = lane >> 4, n = lane & 15;
+  // ---- the entry batch (RkCommon line 0, the tower's line 0): every scalar the id, claim, label,
+  // bias and row-DMA addresses need, loaded together and held at once: one wait in front of the
+  // first vector load (left at their uses, each field is a scalar round trip of its own, the
+  // modulus inside its branch)
+  const RkCommon& C = a.rk.c;
+  const RkTower& T = a.rk.tw[t];  // t is wave-uniform: one scalar offset selects the record
+  const int64_t B = C.B;
+  const void* const labels = C.labels;
+  const int label_dtype = C.label_dtype, gid_dtype = C.gid_dtype;
+  const void* const idcol = T.idcol;
+  const void* const tab0 = T.tab;
+  const int64_t gmod = T.gmod;
+  const float* const b0p = T.b0;
+  const float* const b1p = T.b1;
+  const int32_t* const claim = T.claim;
+  const int32_t* const pos_out = T.pos_out;
+  const int64_t pstride = T.rstride;
+  const int nwg = C.nwg;
+  if (UPD) asm volatile("" ::"s"(nwg), "s"(B), "s"(labels), "s"(label_dtype), "s"(gid_dtype), "s"(idcol), "s"(tab0), "s"(gmod), "s"(b0p), "s"(b1p), "s"(claim));
+  else if (IDX) asm volatile("" ::"s"(nwg), "s"(B), "s"(labels), "s"(label_dtype), "s"(idcol), "s"(tab0), "s"(b0p), "s"(b1p), "s"(pos_out));
+  else if (POOL) asm volatile("" ::"s"(nwg), "s"(B), "s"(labels), "s"(label_dtype), "s"(tab0), "s"(b0p), "s"(b1p), "s"(pstride));
+  else asm volatile("" ::"s"(nwg), "s"(B), "s"(labels), "s"(label_dtype), "s"(gid_dtype), "s"(idcol), "s"(tab0), "s"(gmod), "s"(b0p), "s"(b1p));
   // the tile: XCD x runs tiles [x n / 8, (x + 1) n / 8) (xcd_remap), so the 256-row slices the
   // tail's T2 tiles read (also placed a contiguous 1/8 per XCD) were written through that XCD's L2
-  const int tile = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-  const int64_t B = a.B, m0 = (int64_t)tile * TR, m = m0 + 16 * h + n;
+  // (the grid size from the record: the launch's own copy is a scalar load, and a wait, of its own)
+  const int tile = xcd_remap((int)blockIdx.x, nwg);
+  const int64_t m0 = (int64_t)tile * TR, m = m0 + 16 * h + n;
   const bool live = m < B;
   RK_STAMP(0);
   // ---- 0. loads in dependency order (vmcnt retires in issue order: a wait for a load also waits
   // for everything issued before it): the ids, the label, the biases (raw: no conversion between
   // them); the row (the weight image is the image wave's, above)
-  const bool wide = a.gid_dtype == TT_I64;
+  const bool wide = gid_dtype == TT_I64;
   const int64_t mc = live ? m : 0;  // dead rows of a ragged tile read row 0 of every column
   RkRaw id_raw{0u, 0u}, pout_raw{0u, 0u};
   if (IDX) {
-    id_raw.lo = (uint32_t)(t ? a.gpos[1] : a.gpos[0])[mc];
-    pout_raw.lo = a.gpos_out[0] ? (uint32_t)(t ? a.gpos_out[1] : a.gpos_out[0])[mc] : id_raw.lo;
+    id_raw.lo = (uint32_t) reinterpret_cast<const int32_t*>(idcol)[mc];
+    pout_raw.lo = pos_out ? (uint32_t)pos_out[mc] : id_raw.lo;
   } else if (!POOL) {
-    id_raw = rk_raw(t ? a.gcol[1] : a.gcol[0], wide, mc);
+    id_raw = rk_raw(idcol, wide, mc);
   }
   // UPD: the claim of this row's lookup in the batch's completed dedup table (no dependency: issued
   // beside the id, so the slot word's load can follow the row DMA instead of stalling the chain after
   // layer 1 for a whole memory round trip)
   int32_t cl = -1;
-  if (UPD) cl = a.dd.claim[live ? t * B + m : 0];
-  const RkRaw lab_raw = rk_raw(a.labels, a.label_dtype == TT_I64, mc);
+  if (UPD) cl = claim[mc];
+  const RkRaw lab_raw = rk_raw(labels, label_dtype == TT_I64, mc);
   f32x4 b0v[8], b1v[4];
   auto load_biases = [&]() {
-    const float* b0p = a.params + a.boff[t][0];
-    const float* b1p = a.params + a.boff[t][1];
 #pragma unroll
     for (int mt = 0; mt < 8; ++mt) b0v[mt] = *reinterpret_cast<const f32x4*>(b0p + 32 * (mt >> 1) + 8 * q + 4 * (mt & 1));
 #pragma unroll
@@ -1683,40 +1776,59 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     r = live ? (int64_t)(int32_t)id_raw.lo : -1;
   } else {
     const int64_t id = live ? rk_id(id_raw, wide) : 0;
-    r = id != 0 ? py_mod64(id, t ? a.gmod[1] : a.gmod[0]) : -1;
+    r = id != 0 ? py_mod64(id, gmod) : -1;
   }
-  const float* tab = POOL ? a.pooled + a.s.in_col[t] : (t ? a.gtab[1] : a.gtab[0]);
-  const int64_t rstride = POOL ? a.ldp : IN;  // floats between consecutive source rows
+  const float* tab = reinterpret_cast<const float*>(tab0);
+  const int64_t rstride = POOL ? pstride : IN;  // floats between consecutive source rows
   // the wave's 16 rows -> LDS by LDS-DMA, two whole 512-B rows per wave instruction (two TLB pages
   // per instruction, full lines; a lane-per-row-piece register gather touches 16 rows per
   // instruction): lane l of instruction i carries 16-B chunk (l & 31) ^ row of row 2 i + (l >> 5),
   // so that the B-layout reads below are conflict-free; rows without an id read table row 0
   // (ignored)
+  RK_STAMP2(4);  // EXPERIMENT: the ids landed (r is computed), in front of the row-index shuffles
+  __builtin_amdgcn_sched_barrier(0);
   float* xw = xr[wid];
   // (IN = 64: four 256-B rows per instruction)
   constexpr int CPR = IDX ? IN / 8 : IN / 4;  // 16-B chunks per row (chunk swizzle: c ^ (row & (CPR - 1)))
   constexpr int RPI = 64 / CPR;               // rows per wave instruction
+  constexpr int NDMA = 16 / RPI;              // wave instructions for the 16 rows
+  // every row-index shuffle first, all addresses held at once (rk_pin), then the DMAs back to
+  // back: one LDS round trip between "ids landed" and "rows issued", not one per instruction
   if (IDX) {
     // bf16 rows (2 IN bytes): lane l carries 16-B chunk (l % CPR) ^ row of row RPI i + l / CPR
     const int rr0 = lane / CPR, pc = lane % CPR;
-    const char* src0 = reinterpret_cast<const char*>(t ? a.gsrc[1] : a.gsrc[0]);
+    const char* src0 = reinterpret_cast<const char*>(tab0);
+    const char* src[NDMA];
+    int64_t rid[NDMA];
 #pragma unroll
-    for (int i = 0; i < 16 / RPI; ++i) {
+    for (int i = 0; i < NDMA; ++i) rid[i] = __shfl((long long)r, RPI * i + rr0, 64);
+    rk_pin<NDMA>(rid);
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i) {
       const int row = RPI * i + rr0;
-      const int64_t rid = __shfl((long long)r, row, 64);
-      const char* src = src0 + (rid >= 0 ? rid : 0) * (IN * 2) + 16 * (pc ^ (row & (CPR - 1)));
-      __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(reinterpret_cast<char*>(xw) + i * 1024), 16, 0, 0);
+      src[i] = src0 + (rid[i] >= 0 ? rid[i] : 0) * (IN * 2) + 16 * (pc ^ (row & (CPR - 1)));
     }
+    rk_pin<NDMA>(src);
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i)
+      __builtin_amdgcn_global_load_lds((glb_void*)src[i], (lds_void*)(reinterpret_cast<char*>(xw) + i * 1024), 16, 0, 0);
   } else {
     const int rr0 = lane / CPR, pc = lane % CPR;
+    const float* src[NDMA];
+    int64_t rid[NDMA];
 #pragma unroll
-    for (int i = 0; i < 16 / RPI; ++i) {
+    for (int i = 0; i < NDMA; ++i) rid[i] = __shfl((long long)r, RPI * i + rr0, 64);
+    rk_pin<NDMA>(rid);
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i) {
       const int row = RPI * i + rr0;
-      const int64_t rid = __shfl((long long)r, row, 64);
-      const float* src = tab + (rid >= 0 ? rid : 0) * rstride + 4 * (pc ^ row);
-      if (!TDBG(32))  // EXPERIMENT (timing only, garbage rows): no row gather
-        __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(xw + i * 256), 16, 0, 0);
+      src[i] = tab + (rid[i] >= 0 ? rid[i] : 0) * rstride + 4 * (pc ^ row);
     }
+    rk_pin<NDMA>(src);
+#pragma unroll
+    for (int i = 0; i < NDMA; ++i)
+      if (!TDBG(32))  // EXPERIMENT (timing only, garbage rows): no row gather
+        __builtin_amdgcn_global_load_lds((glb_void*)src[i], (lds_void*)(xw + i * 256), 16, 0, 0);
   }
   __builtin_amdgcn_sched_barrier(0);
   // the classic step's insert of this batch's lookups (T1 with a dedup workspace): the claiming
@@ -1730,7 +1842,19 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     dd_insert_begin(a.dd, key, li, pend);
   }
   RK_STAMP(1);
+  // ---- the late batch (the rest of RkCommon line 0, the tower's line 1 up to the state): the strip
+  // bases, the slots, the state, grad_scale — issued behind the row DMAs, so their round trip runs
+  // inside the wait for the rows (the pin behind that wait only keeps the loads in this block)
+  const int in_max = C.in_max;
+  const float grad_scale = C.grad_scale, fB = C.fB;
+  DSlot* const slots = C.slots;
+  __bf16* const xt_t = T.xt;
+  __bf16* const act_t = T.act0;
+  const float* const us_t = T.us;
+  __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the rows (LDS-DMA) and the small loads
+  if (UPD) asm volatile("" ::"s"(in_max), "s"(grad_scale), "s"(fB), "s"(slots), "s"(xt_t), "s"(act_t), "s"(us_t));
+  else asm volatile("" ::"s"(in_max), "s"(grad_scale), "s"(fB), "s"(xt_t), "s"(act_t));
   RK_STAMP(2);
   __syncthreads();  // barrier 1: the image wave's DMAs landed before it arrived
   RK_STAMP(3);
@@ -1764,12 +1888,13 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   float s_old = 0.f;
   if (UPD) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {  // the table's hot-row count for the tail (dd_update_block)
-      const int32_t nh = a.dd.ctr[0];
-      a.dd.ctr[2] = nh;
-      a.dd.ctr[0] = 0;
+      int32_t* const ctr = C.ctr;
+      const int32_t nh = ctr[0];
+      ctr[2] = nh;
+      ctr[0] = 0;
     }
-    word = reinterpret_cast<const uint32_t*>(&a.dd.slots[cl >= 0 ? cl : 0].word)[0];
-    s_old = (t ? a.us[1] : a.us[0])[r >= 0 ? r : 0];
+    word = reinterpret_cast<const uint32_t*>(&slots[cl >= 0 ? cl : 0].word)[0];
+    s_old = us_t[r >= 0 ? r : 0];
   }
   __builtin_amdgcn_sched_barrier(0);
   const char* img0 = wimg + t * RK_IMG_T;
@@ -1778,7 +1903,7 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   f32x4 acc[8];
   // the T1 -> T2 strip of X (row-major), fire-and-forget: issued before the layer's MFMAs so the
   // stores drain under them (likewise h's after layer 0, the dZ strips before dX)
-  if (!TDBG(512)) rk_strip<NI>(xb, a.xt + (int64_t)t * a.in_max * a.Bp + m * a.in_max, q);  // (TDBG: timing only)
+  if (!TDBG(512)) rk_strip<NI>(xb, xt_t + m * in_max, q);  // (TDBG: timing only)
   rk_gemm<8, NI, false>(acc, img0, xb, lane);
   RK_STAMP(4);
   bf16x8 hb[4];
@@ -1792,7 +1917,7 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     }
     hb[s] = rk_pack(u0, u1);
   }
-  if (!TDBG(256)) rk_strip<4>(hb, a.act + ((int64_t)t * MAXL + 0) * MAXW * a.Bp + m * MAXW, q);
+  if (!TDBG(256)) rk_strip<4>(hb, act_t + m * MAXW, q);
   // ---- 2. layer 1: out^T = relu(W1 h^T + b1) (fp32), 4 M-tiles x 4 k-steps; exchanged in LDS
   f32x4 uo[4];
   rk_gemm<4, 4, false>(acc, img1, hb, lane);
@@ -1835,15 +1960,18 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   const float d = c0 + c1;
   float lo = 0.f, dl = 0.f;
   if (live) {
-    const float x = d, y = rk_label(lab_raw, a.label_dtype);
+    const float x = d, y = rk_label(lab_raw, label_dtype);
     const float e = __expf(-fabsf(x));
     const float l1p = e < 1e-4f ? e * (1.f - 0.5f * e) : __logf(1.f + e);
     const float lsig = fminf(x, 0.f) - l1p;
     lo = (1.f - y) * x - lsig;
     const float rc = __builtin_amdgcn_rcpf(1.f + e);
-    dl = ((x >= 0.f ? rc : e * rc) - y) * (a.grad_scale / (float)B);
+    dl = ((x >= 0.f ? rc : e * rc) - y) * (grad_scale / fB);
   }
-  if (t == 0 && q == 0) lrow[16 * h + n] = lo;
+  // (the row half per lane from here on: the wave-uniform copy would hold a scalar register from
+  // the entry to the end)
+  const int hv = (int)(threadIdx.x >> 6) & 1;
+  if (t == 0 && q == 0) lrow[16 * hv + n] = lo;
   // ---- 4. dZ1 = dlogit * other * (self > 0) (fp32: bias sums; bf16: the next product, the strip)
   float z1[16];
   bf16x8 z1b[4];
@@ -1860,7 +1988,18 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   }
   // ---- 5. dZ0^T = (W1^T dZ1^T) * (h > 0): 8 M-tiles x 2 k-steps
   RK_STAMP(8);
+  // ---- the update batch (the rest of the tower's line 1, the table rows, RkCommon line 1), issued
+  // in front of this product, whose LDS waits cover their round trip (the pin behind the product
+  // keeps the loads here instead of at their uses, the list's inside its branch)
+  __bf16* const dzt0_t = T.dzt0;
+  __bf16* const dzt1_t = T.dzt1;
+  float* const uw_t = T.uw;
+  const float ulr = C.ulr, ueps = C.ueps;
+  int32_t* const multi = C.multi;
+  const int nseg = C.nseg;
   rk_gemm<8, 2, true>(acc, img1, z1b, lane);
+  if (UPD) asm volatile("" ::"s"(dzt0_t), "s"(dzt1_t), "s"(uw_t), "s"(ulr), "s"(ueps), "s"(multi), "s"(nseg));
+  else asm volatile("" ::"s"(dzt0_t), "s"(dzt1_t));
   float z0[32];
   bf16x8 z0b[4];
 #pragma unroll
@@ -1877,24 +2016,43 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   }
   // the dZ strips (T1 -> T2), issued here so they drain beside dX and the row update instead of at
   // the kernel's end
-  if (!TDBG(512)) rk_strip<2>(z1b, a.dzt + ((int64_t)t * MAXL + 1) * MAXW * a.Bp + m * MAXW, q);
-  if (!TDBG(128)) rk_strip<4>(z0b, a.dzt + ((int64_t)t * MAXL + 0) * MAXW * a.Bp + m * MAXW, q);
+  if (!TDBG(512)) rk_strip<2>(z1b, dzt1_t + m * MAXW, q);
+  if (!TDBG(128)) rk_strip<4>(z0b, dzt0_t + m * MAXW, q);
   // ---- 6. dX^T = W0^T dZ0^T: 8 M-tiles x 4 k-steps; acc[mt] = dX features of xv[mt]
   RK_STAMP(9);
+  // ---- the gradient rows and the epilogue's pointers (lines the update batch brought into the
+  // scalar cache): in front of the dX product; UPD, which has no register to spare across it,
+  // fetches them under the write-back's one LDS wait, in front of the row stores
+  float* grow_t = nullptr;
+  float* prow_t = nullptr;
+  int64_t ldp = 0;
+  float* db0_t = nullptr;
+  float* db1_t = nullptr;
+  float* logits = nullptr;
+  float* loss_part = nullptr;
+  if constexpr (!UPD) {
+    grow_t = T.grow;
+    prow_t = T.prow;
+    ldp = C.ldp;
+    db0_t = T.db0;
+    db1_t = T.db1;
+    logits = C.logits;
+    loss_part = C.loss_part;
+  }
   rk_gemm<MTI, 4, true>(acc, img0, z0b, lane);
+  if constexpr (!UPD) asm volatile("" ::"s"(grow_t), "s"(prow_t), "s"(ldp), "s"(db0_t), "s"(db1_t), "s"(logits), "s"(loss_part));
   RK_STAMP(10);
   // ---- 7. the row: UPD + looked up once -> row-wise Adagrad in place (the K3 update's arithmetic and
   // summation tree: feature groups of 4 combined at group bits 4, 3 (in lane), 2, 1 (lanes ^ 32,
   // ^ 16), 0 (in lane)); otherwise dX -> the pooled gradient (and the gathered row, pooled_out)
-  float* grow;
+  float* grow = nullptr;
   bool store_dx;
   if (IDX) {  // dX -> the requester's gradient row in the send buffer (none for a zero row)
     const int32_t po = (int32_t)pout_raw.lo;
     store_dx = r >= 0 && po >= 0;
-    grow = (t ? a.gdst[1] : a.gdst[0]) + (int64_t)(store_dx ? po : 0) * IN;
+    grow = grow_t + (int64_t)(store_dx ? po : 0) * IN;
     if (a.xd.W) grow = reinterpret_cast<float*>(px_row(a.xd, store_dx ? po : 0, IN * 4));
   } else {
-    grow = live ? a.gpooled + m * a.ldp + a.s.in_col[t] : nullptr;
     store_dx = live;
   }
   if (UPD) {
@@ -1917,7 +2075,7 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     RK_STAMP2(0);
     const float sq = e2[0] + e2[1];
     const float snew = rw_state(s_old, sq, IN);
-    const float step = rw_step(snew, a.ulr, a.ueps);
+    const float step = rw_step(snew, ulr, ueps);
     const uint32_t cnt = word & (uint32_t)DD_CNT_MASK;
     const bool single = r >= 0 && cl >= 0 && cnt == 1u;
     {
@@ -1926,9 +2084,9 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
       const bool mul = q == 0 && r >= 0 && cl >= 0 && cnt >= 2u && cnt <= (uint32_t)DD_INL;
       const uint64_t bal = __ballot(mul);
       const int seg = tile * 4 + wid;
-      if (seg < a.dd.nseg) {  // [count, slots...] (DD_SEGW): the list role reads count + 3 slots at once
-        if (mul) a.dd.multi[(int64_t)seg * DD_SEGW + 1 + __popcll(bal & ((1ull << lane) - 1))] = cl;
-        if (lane == 0) a.dd.multi[(int64_t)seg * DD_SEGW] = __popcll(bal);
+      if (seg < nseg) {  // [count, slots...] (DD_SEGW): the list role reads count + 3 slots at once
+        if (mul) multi[(int64_t)seg * DD_SEGW + 1 + __popcll(bal & ((1ull << lane) - 1))] = cl;
+        if (lane == 0) multi[(int64_t)seg * DD_SEGW] = __popcll(bal);
       }
     }
     // the updated rows go back through the wave's LDS rows (same chunk swizzle) and out as two
@@ -1942,34 +2100,52 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     asm volatile("" ::: "memory");  // LDS is in order per wave: only the compiler must not reorder
     {
       const int rr0 = lane / CPR, pc = lane % CPR;
-      float* wtab = t ? a.uw[1] : a.uw[0];
+      float* wtab = uw_t;
+      // as a batch: every shuffle (the row's index where it is updated here, -1 elsewhere: one
+      // value carries the index and the predicate), every LDS read, one wait; then the stores under
+      // their predicates, with no LDS instruction and no wait between them
+      const int64_t rsend = single ? r : -1;
+      int64_t rid[NDMA];
+      f32x4 w[NDMA];
+      grow_t = T.grow;
+      prow_t = T.prow;
+      ldp = C.ldp;
+      db0_t = T.db0;
+      db1_t = T.db1;
+      logits = C.logits;
+      loss_part = C.loss_part;
 #pragma unroll
-      for (int i = 0; i < 16 / RPI; ++i) {
+      for (int i = 0; i < NDMA; ++i) rid[i] = __shfl((long long)rsend, RPI * i + rr0, 64);
+#pragma unroll
+      for (int i = 0; i < NDMA; ++i) w[i] = *reinterpret_cast<const f32x4*>(xw + (RPI * i + rr0) * IN + 4 * pc);
+      rk_pin<NDMA>(rid);
+      rk_pin<NDMA>(w);
+      asm volatile("" ::"s"(grow_t), "s"(prow_t), "s"(ldp), "s"(db0_t), "s"(db1_t), "s"(logits), "s"(loss_part));
+#pragma unroll
+      for (int i = 0; i < NDMA; ++i) {
         const int row = RPI * i + rr0;
-        const int64_t rid = __shfl((long long)r, row, 64);
-        const int sg = __shfl((int)single, row, 64);
-        const f32x4 w = *reinterpret_cast<const f32x4*>(xw + row * IN + 4 * pc);
-        if (sg) *reinterpret_cast<f32x4*>(wtab + rid * IN + 4 * (pc ^ row)) = w;
+        if (__builtin_expect(rid[i] >= 0, 1)) *reinterpret_cast<f32x4*>(wtab + rid[i] * IN + 4 * (pc ^ row)) = w[i];
       }
     }
     RK_STAMP2(2);
     if (single) {
       if (q == 0) {
-        (t ? a.us[1] : a.us[0])[r] = snew;
-        a.dd.slots[cl].word = DD_EMPTY;  // free: nothing else of the step reads a single slot
+        const_cast<float*>(us_t)[r] = snew;
+        slots[cl].word = DD_EMPTY;  // free: nothing else of the step reads a single slot
       }
-      store_dx = a.pooled_out != nullptr;  // dX only for inspection
+      store_dx = prow_t != nullptr;  // dX only for inspection
     }
   }
+  if (!IDX) grow = grow_t + m * ldp;  // (store_dx: live rows only)
   if (store_dx) {
 #pragma unroll
     for (int mt = 0; mt < MTI; ++mt)
       *reinterpret_cast<f32x4*>(grow + 32 * (mt >> 1) + 8 * q + 4 * (mt & 1)) = acc[mt];
   }
   RK_STAMP2(3);
-  if (t == 0 && q == 0 && live) a.logits[m] = d;  // after the row update (see rk_strip)
-  if (!IDX && !POOL && a.pooled_out && live) {
-    float* prow = a.pooled_out + m * a.ldp + a.s.in_col[t];
+  if (t == 0 && q == 0 && live) logits[m] = d;  // after the row update (see rk_strip)
+  if (!IDX && !POOL && prow_t && live) {
+    float* prow = prow_t + m * ldp;
 #pragma unroll
     for (int mt = 0; mt < MTI; ++mt) *reinterpret_cast<f32x4*>(prow + 32 * (mt >> 1) + 8 * q + 4 * (mt & 1)) = xv[mt];
   }
@@ -1981,7 +2157,7 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   rk_colsum<16>(z1, n);  // lane n: k = n
   // feature of value k = 4 mt + j: 32 (mt >> 1) + 8 q + 4 (mt & 1) + j
   auto feat = [&](int k) { return 32 * ((k >> 2) >> 1) + 8 * q + 4 * ((k >> 2) & 1) + (k & 3); };
-  if (h == 1) {
+  if (hv == 1) {
     bsum[t][feat(2 * n)] = z0[0];
     bsum[t][feat(2 * n + 1)] = z0[1];
     bsum[t][RK_W0 + feat(n)] = z1[0];
@@ -1989,16 +2165,16 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   RK_STAMP(13);
   __syncthreads();
   RK_STAMP(14);
-  if (h == 0) {
-    float* db0 = a.dbpart + (((int64_t)t * MAXL + 0) * a.nwg + tile) * MAXW;  // by tile: T2 sums them in tile order
-    float* db1 = a.dbpart + (((int64_t)t * MAXL + 1) * a.nwg + tile) * MAXW;
+  if (hv == 0) {
+    float* db0 = db0_t + (int64_t)tile * MAXW;  // by tile: T2 sums them in tile order
+    float* db1 = db1_t + (int64_t)tile * MAXW;
     db0[feat(2 * n)] = z0[0] + bsum[t][feat(2 * n)];
     db0[feat(2 * n + 1)] = z0[1] + bsum[t][feat(2 * n + 1)];
     db1[feat(n)] = z1[0] + bsum[t][RK_W0 + feat(n)];
     if (t == 0 && lane == 0) {
       float p = 0.f;
       for (int i = 0; i < TR; ++i) p += lrow[i];
-      a.loss_part[tile] = p;
+      loss_part[tile] = p;
     }
   }
   // every row's overflow entry is written (EMPTY for a dropped id or a dead row of a ragged tile):
@@ -3194,6 +3370,50 @@ struct T1Common {
   void* stream;
 };
 
+// the row-owned T1's argument front from the filled TowerArgs (gather, indexed or pooled input)
+static void rk_front(TowerArgs& a, bool pool) {
+  RkCommon& c = a.rk.c;
+  c.B = a.B;
+  c.labels = a.labels;
+  c.label_dtype = a.label_dtype;
+  c.gid_dtype = a.gid_dtype;
+  c.grad_scale = a.grad_scale;
+  c.in_max = (int32_t)a.in_max;
+  c.slots = a.dd.slots;
+  c.ctr = a.dd.ctr;
+  c.ulr = a.ulr;
+  c.nwg = a.nwg;
+  c.fB = (float)a.B;
+  c.ueps = a.ueps;
+  c.ldp = a.ldp;
+  c.multi = a.dd.multi;
+  c.logits = a.logits;
+  c.loss_part = a.loss_part;
+  c.nseg = a.dd.nseg;
+  const bool idx = a.gpos[0] != nullptr;
+  for (int t = 0; t < 2; ++t) {
+    RkTower& w = a.rk.tw[t];
+    w.idcol = idx ? static_cast<const void*>(a.gpos[t]) : a.gcol[t];
+    w.tab = idx ? static_cast<const void*>(a.gsrc[t]) : pool ? static_cast<const void*>(a.pooled + a.s.in_col[t]) : a.gtab[t];
+    w.gmod = a.gmod[t];
+    w.b0 = a.params + a.boff[t][0];
+    w.b1 = a.params + a.boff[t][1];
+    w.claim = a.uw[0] ? a.dd.claim + (int64_t)t * a.B : nullptr;
+    w.pos_out = a.gpos_out[0] ? a.gpos_out[t] : nullptr;
+    w.rstride = a.ldp;
+    w.xt = a.xt + (int64_t)t * a.in_max * a.Bp;
+    w.act0 = a.act + ((int64_t)t * MAXL + 0) * MAXW * a.Bp;
+    w.dzt0 = a.dzt + ((int64_t)t * MAXL + 0) * MAXW * a.Bp;
+    w.dzt1 = a.dzt + ((int64_t)t * MAXL + 1) * MAXW * a.Bp;
+    w.us = a.us[t];
+    w.uw = a.uw[t];
+    w.grow = idx ? a.gdst[t] : a.gpooled + a.s.in_col[t];
+    w.prow = a.pooled_out ? a.pooled_out + a.s.in_col[t] : nullptr;
+    w.db0 = a.dbpart + ((int64_t)t * MAXL + 0) * a.nwg * MAXW;
+    w.db1 = a.dbpart + ((int64_t)t * MAXL + 1) * a.nwg * MAXW;
+  }
+}
+
 // shared by every T1 export: checks, T1 arguments, launch
 static int launch_t1(const tt_tower_shape_t* shape, int64_t B, TowerArgs& a, const float* pooled, int64_t ldp,
                      float* gpooled, const T1Common& c) {
@@ -3285,6 +3505,7 @@ static int launch_t1(const tt_tower_shape_t* shape, int64_t B, TowerArgs& a, con
 #endif
   if (rows_t1) {
     a.wimg = ws + L.o_wimg;
+    rk_front(a, false);
     if (a.gpos[0])
       i0 == 64 ? tower_rows_kernel<false, true, 64><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a)
                : tower_rows_kernel<false, true, 128><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a);
@@ -3301,6 +3522,7 @@ static int launch_t1(const tt_tower_shape_t* shape, int64_t B, TowerArgs& a, con
 #endif
   if (rows_pool && rows_pool_ok) {
     a.wimg = ws + L.o_wimg;
+    rk_front(a, true);
     i0 == 64 ? tower_rows_kernel<false, false, 64, true><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a)
              : tower_rows_kernel<false, false, 128, true><<<g, dim3(RK_THREADS), 0, as_stream(stream)>>>(a);
     return check_launch("tower_rows_pooled");
