@@ -76,7 +76,7 @@ def _check_invariants(idx, items, assign=None):
 
 
 @pytest.mark.parametrize("with_bias", [False, True], ids=["nobias", "bias"])
-@pytest.mark.parametrize("E", [32, 64, 128])
+@pytest.mark.parametrize("E", [32, 64, 96, 128])
 def test_scan_equals_filtered_exact(device, E, with_bias):
     M, N, nlist, k = 40, 3000, 8, 100
     Q, Cm = ro.make_inputs(M, N, E, 300 + E)

@@ -97,7 +97,7 @@ def _cpu_mask_lists(idx, mask):
 
 
 @pytest.mark.parametrize("with_bias", [False, True], ids=["nobias", "bias"])
-@pytest.mark.parametrize("E", [32, 64, 128])
+@pytest.mark.parametrize("E", [32, 64, 96, 128])
 def test_masked_scan_equals_filtered_exact(device, E, with_bias):
     M, N, nlist, k = 40, 3000, 8, 100
     assert N % 32

@@ -29,7 +29,7 @@ ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["api.cpp", "kjt.hip", "embedding.hip", "gemm.hip", "loss_adam.hip", "tower.hip", "dedup.hip", "shard.hip", "shard_kjt.hip", "peer.hip", "retrieval.hip", "ivf.hip"]
-HEADERS = [CSRC / "tt_common.h", CSRC / "dedup.h", CSRC / "shard.h", CSRC / "topk_common.h", INCLUDE / "tt_mi355x.h"]
+HEADERS = [CSRC / "tt_common.h", CSRC / "dedup.h", CSRC / "shard.h", CSRC / "topk_common.h", CSRC / "topk_scan.h", INCLUDE / "tt_mi355x.h"]
 
 CFLAGS = [
     "-O3",

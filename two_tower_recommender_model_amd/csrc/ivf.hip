@@ -6,15 +6,12 @@
 // The index stores the item rows in list order (bf16, a list's rows contiguous, its original item
 // indices `labels` ascending). A (query, probed list) PAIR is the unit of work: the pairs are grouped
 // by list in the workspace (count, exclusive scan, scatter), so that a workgroup streams ONE list
-// past a tile of up to 128 of the queries that probe it. From there it is the exact kernel's
-// structure (retrieval.hip): each wave's 32 queries as MFMA B fragments in registers, the list's
-// rows through double-buffered LDS chunks, v_mfma_f32_16x16x32_bf16 in ascending k-steps from a zero
-// accumulator, + bias, the max3 + max + compare filter, a 32-key candidate buffer per query and the
-// rank-counting merge into the pair's sorted partial list (k keys at ws + p * k). Keys carry the
-// ORIGINAL item index (labels[n], loaded in the candidate branch), so the order "higher score, then
-// lower original index" and the exclusion lists work on item indices; labels ascend within a list,
-// so the strict compare against the threshold still loses nothing. A last kernel merges a query's
-// up to 64 partial lists (one lane per probe, k rounds of a wave-wide max).
+// past a tile of up to 128 of the queries that probe it, through the shared scan (topk_scan.h); a
+// pair's sorted partial list is the k keys at ws + p * k. Keys carry the ORIGINAL item index
+// (labels[n], loaded in the candidate branch), so the order "higher score, then lower original
+// index" and the exclusion lists work on item indices; labels ascend within a list, so the scan's
+// strict compare against the threshold still loses nothing. A last kernel merges a query's up to 64
+// partial lists (one lane per probe).
 //
 // The score of a pair is the same function of the two rows' bf16 values and the bias as in
 // tt_topk_mips, and the result is unique under the total order: it is what tt_topk_mips_filtered
@@ -26,13 +23,10 @@
 //
 // The item mask (tt_ivf_scan_masked): a bit per PACKED row, row_allow, which tt_ivf_mask_lists makes
 // from the mask over original item indices and the labels. A list begins at a multiple of 128, so a
-// chunk's bits are whole aligned words: they are loaded with the chunk's other global loads, staged
-// beside its bias, read with the tile's other LDS reads and ANDed into the candidate test, as the
-// exact kernel does with its mask. A denied row never enters a candidate buffer.
+// chunk's bits are whole aligned words: they are loaded with the chunk's other global loads and are
+// the scan's row mask.
 #include "tt_common.h"
-#include "topk_common.h"
-
-#include <limits>
+#include "topk_scan.h"
 
 namespace tt {
 
@@ -166,21 +160,70 @@ struct IvfMaskArgs : IvfArgs {
   const uint32_t* row_allow;
 };
 
+// a workgroup's work unit for the shared scan (topk_scan.h): a wave's pairs against their list
+template <int KS, bool MASK>
+struct IvfSrc {
+  using Sh = ScanShape<KS>;
+  const std::conditional_t<MASK, IvfMaskArgs, IvfArgs>& a;
+  const int* qid;  // [TK_QW] the wave's pairs' queries, -1: no pair
+  int pw;          // the wave's pairs: none in a tile's tail waves
+  u64* lists;
+  int64_t n_beg, n_end;
+  int nchunks;
+  bool wave_excl;
+  const int32_t* excl_values;
+  // MASK: thread t stages word t % MW of a chunk (every thread one, without a branch: the FILT
+  // instantiations have no scalar register left for one more saved exec mask). Its index within the
+  // list's words (n_beg is a multiple of 32) is clamped to the list's last word: a word that begins
+  // at or past n_end is not read and counts as zero
+  const uint32_t* mask_p;
+  int mask_i, mask_last;
+  // staging: thread t holds 8-element groups g = t + TK_THREADS i of the chunk: item row g / GPR.
+  // The rows are bf16 already: 16-byte loads, stored as they are
+  bf16x8 rawb[Sh::GPT];
+  uint32_t rawmask;
+
+  __device__ __forceinline__ bool computes() const { return pw > 0; }
+  __device__ __forceinline__ int64_t query(int q) const { return qid[q]; }
+  __device__ __forceinline__ int index(int64_t n) const { return a.labels[n]; }
+  __device__ __forceinline__ bool has_list(int q) const { return q < pw; }
+  __device__ __forceinline__ const int64_t* excl(int q) const { return a.excl_offsets + __builtin_amdgcn_readfirstlane(qid[q]); }
+
+  __device__ __forceinline__ void load_rows(int64_t n0, int tid) {
+#pragma unroll
+    for (int i = 0; i < Sh::GPT; ++i) {
+      const int g = tid + TK_THREADS * i;
+      const int row = g / Sh::GPR, kc = (g - row * Sh::GPR) * 8;
+      const int64_t n = n0 + row;
+      bf16x8 z;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) z[j] = (__bf16)0.f;
+      rawb[i] = n < n_end ? *reinterpret_cast<const bf16x8*>(a.rows + n * Sh::E + kc) : z;
+    }
+  }
+  __device__ __forceinline__ void store_rows(__bf16* buf, int tid) const {
+#pragma unroll
+    for (int i = 0; i < Sh::GPT; ++i) {
+      const int g = tid + TK_THREADS * i;
+      const int row = g / Sh::GPR, kc = (g - row * Sh::GPR) * 8;
+      *reinterpret_cast<bf16x8*>(&buf[row * Sh::STRIDE + kc]) = rawb[i];
+    }
+  }
+  __device__ __forceinline__ void load_mask(int c, int64_t, int) {
+    const int wd = c * Sh::MW + mask_i;  // chunks are loaded only where len > 0: mask_last >= 0
+    const uint32_t x = mask_p[min(wd, mask_last)];
+    rawmask = wd <= mask_last ? x : 0u;
+  }
+  __device__ __forceinline__ void store_mask(uint32_t* words, int) const {
+    words[mask_i] = rawmask;  // the threads of one word store the same value
+  }
+};
+
 template <int KS, bool BIAS, bool FILT, bool MASK>
 __global__ void __launch_bounds__(TK_THREADS, 2)
     ivf_scan_kernel(const std::conditional_t<MASK, IvfMaskArgs, IvfArgs> a) {
-  constexpr int E = KS * 32, STRIDE = E + 8, GPR = E / 8;  // GPR: 8-element groups per item row
-  constexpr int TK_IC = tk_chunk(E);
-  constexpr int GPT = TK_IC * GPR / TK_THREADS;             // groups per thread
-  __shared__ __attribute__((aligned(16))) __bf16 items[2][TK_IC * STRIDE];
-  __shared__ __attribute__((aligned(16))) float bias_s[2][TK_IC];
-  __shared__ uint32_t mask_s[2][4];  // MASK: the chunk's TK_IC / 32 mask words (no LDS without MASK)
-  __shared__ u64 cbuf_s[TK_WAVES][TK_QW * TK_CB];
-  __shared__ u64 lscr_s[TK_WAVES][TT_TOPK_MAX_K];
-  __shared__ int ccnt_s[TK_WAVES][TK_QW];
-  __shared__ int lcnt_s[TK_WAVES][TK_QW];
-  __shared__ float thrs_s[TK_WAVES][TK_QW];
-  __shared__ int qid_s[TK_WAVES][TK_QW];  // the wave's pairs' queries, -1: no pair
+  constexpr int TK_IC = ScanShape<KS>::IC;
+  __shared__ int qid_s[TK_WAVES][TK_QW];
 
   // the grid is an upper bound of the tiles; the tiles of one list are consecutive in the logical
   // order, which an XCD runs a contiguous part of: they share the list's rows through its L2
@@ -200,7 +243,7 @@ __global__ void __launch_bounds__(TK_THREADS, 2)
   const int p_beg = a.list_off[l] + (b - a.tile_off[l]) * TK_QB;
   const int p_end = min(a.list_off[l + 1], p_beg + TK_QB);
   const int p_wave = p_beg + wid * TK_QW;
-  const int pw = max(0, min(TK_QW, p_end - p_wave));  // the wave's pairs: none in a tile's tail waves
+  const int pw = max(0, min(TK_QW, p_end - p_wave));
   // a list that does not lie within the P rows is empty
   int64_t n_beg = a.list_begin[l];
   int len = a.list_len[l];
@@ -215,21 +258,13 @@ __global__ void __launch_bounds__(TK_THREADS, 2)
       len = 0;
     }
   }
-  const int64_t n_end = n_beg + len;
-  const int nchunks = (len + TK_IC - 1) / TK_IC;
-  const int k = a.k;
 
-  const WaveSel w{cbuf_s[wid], lscr_s[wid], ccnt_s[wid], lcnt_s[wid], thrs_s[wid]};
   int* qid = qid_s[wid];
-  for (int i = lane; i < TK_QW * TK_CB; i += 64) w.cbuf[i] = 0ull;
   bool lane_excl = false;
   if (lane < TK_QW) {
     int m = lane < pw ? a.pair_query[p_wave + lane] : -1;
     if (m < 0 || m >= a.M) m = -1;
     qid[lane] = m;
-    w.ccnt[lane] = 0;
-    w.lcnt[lane] = 0;
-    w.thrs[lane] = m >= 0 ? -std::numeric_limits<float>::infinity() : std::numeric_limits<float>::infinity();
     if constexpr (FILT) lane_excl = m >= 0 && a.excl_offsets[m + 1] > a.excl_offsets[m];
   }
   // FILT: does any of the wave's queries have a non-empty exclusion segment?
@@ -238,188 +273,21 @@ __global__ void __launch_bounds__(TK_THREADS, 2)
   // topk_drop_excluded wants it anyway: with the mask the scalar registers do not suffice
   const int32_t* excl_values = a.excl_values;
   if constexpr (FILT && MASK) asm volatile("" : "+v"(excl_values));
-  wave_sync();
-
-  // the wave's queries as B operands: lane l holds query (l & 15), k = 32 ks + 8 (l >> 4) + j
-  bf16x8 qf[2][KS];
-  float thr[2];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int64_t m = qid[qt * 16 + (lane & 15)];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      bf16x8 f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float x = 0.f;
-        if (m >= 0) {
-          const int64_t o = m * a.ldq + ks * 32 + (lane >> 4) * 8 + j;
-          x = a.q_bf16 ? __uint_as_float(((uint32_t) reinterpret_cast<const unsigned short*>(a.q)[o]) << 16)
-                       : reinterpret_cast<const float*>(a.q)[o];
-        }
-        f[j] = (__bf16)x;
-      }
-      qf[qt][ks] = f;
-    }
-    thr[qt] = m >= 0 ? -std::numeric_limits<float>::infinity() : std::numeric_limits<float>::infinity();
-  }
-
-  // staging: thread t holds 8-element groups g = t + TK_THREADS i of the chunk: item row g / GPR.
-  // The rows are bf16 already: 16-byte loads, stored as they are
-  bf16x8 rawb[GPT];
-  float rawbias = 0.f;
-  uint32_t rawmask = 0u;
-  // MASK: thread t stages word t % (TK_IC / 32) of a chunk (every thread one, without a branch: the
-  // FILT instantiations have no scalar register left for one more saved exec mask). Its index within
-  // the list's words (n_beg is a multiple of 32) is clamped to the list's last word: a word that
-  // begins at or past n_end is not read and counts as zero
-  constexpr int MW = TK_IC / 32;
-  const int mask_i = tid & (MW - 1), mask_last = (len - 1) >> 5;
   const uint32_t* mask_p = nullptr;
   if constexpr (MASK) {
     mask_p = a.row_allow + (n_beg >> 5);
     asm volatile("" : "+v"(mask_p));  // held in vector registers, for the same reason
   }
-  auto load_chunk = [&](int c) {
-    const int64_t n0 = n_beg + (int64_t)c * TK_IC;
-#pragma unroll
-    for (int i = 0; i < GPT; ++i) {
-      const int g = tid + TK_THREADS * i;
-      const int row = g / GPR, kc = (g - row * GPR) * 8;
-      const int64_t n = n0 + row;
-      bf16x8 z;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) z[j] = (__bf16)0.f;
-      rawb[i] = n < n_end ? *reinterpret_cast<const bf16x8*>(a.rows + n * E + kc) : z;
-    }
-    if (BIAS && tid < TK_IC) rawbias = n0 + tid < n_end ? a.bias[n0 + tid] : 0.f;
-    if constexpr (MASK) {
-      const int wd = c * MW + mask_i;  // load_chunk runs only where len > 0: mask_last >= 0
-      const uint32_t x = mask_p[min(wd, mask_last)];
-      rawmask = wd <= mask_last ? x : 0u;
-    }
-  };
-  auto store_chunk = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < GPT; ++i) {
-      const int g = tid + TK_THREADS * i;
-      const int row = g / GPR, kc = (g - row * GPR) * 8;
-      *reinterpret_cast<bf16x8*>(&items[buf][row * STRIDE + kc]) = rawb[i];
-    }
-    if (BIAS && tid < TK_IC) bias_s[buf][tid] = rawbias;
-    if constexpr (MASK) {
-      mask_s[buf][mask_i] = rawmask;  // the threads of one word store the same value
-    }
-  };
+  wave_sync();
 
-  if (nchunks > 0) {
-    load_chunk(0);
-    store_chunk(0);
-  }
-  __syncthreads();
-
-  for (int c = 0; c < nchunks; ++c) {
-    const int buf = c & 1;
-    if (c + 1 < nchunks) load_chunk(c + 1);
-    const int64_t n0 = n_beg + (int64_t)c * TK_IC;
-    // a wave with no pairs only helps to stage
-    if (pw > 0) {
-#pragma unroll 1
-      for (int it = 0; it < TK_IC / 16; ++it) {
-        bf16x8 af[KS];
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks)
-          af[ks] = *reinterpret_cast<const bf16x8*>(&items[buf][(it * 16 + (lane & 15)) * STRIDE + ks * 32 + (lane >> 4) * 8]);
-        f32x4 bv = (f32x4)(0.f);
-        if (BIAS) bv = *reinterpret_cast<const f32x4*>(&bias_s[buf][it * 16 + (lane >> 4) * 4]);
-        // MASK: the chunk's mask word it >> 1, read with the tile's other LDS reads: not one more
-        // latency inside the candidate branch
-        uint32_t mword = 0u;
-        if constexpr (MASK) mword = mask_s[buf][it >> 1];
-#pragma unroll
-        for (int qt = 0; qt < 2; ++qt) {
-          f32x4 acc = (f32x4)(0.f);
-#pragma unroll
-          for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks], qf[qt][ks], acc, 0, 0, 0);
-          if (BIAS) acc += bv;
-          const float mx = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
-          if (__ballot(mx > thr[qt]) != 0ull) {
-            // candidates of this tile, decided against the threshold as it stood before the tile;
-            // rows past the list's end (its padding, the next list) are cut here
-            const int q = qt * 16 + (lane & 15);
-            const int64_t nb = n0 + it * 16 + (lane >> 4) * 4;
-            bool pass[4];
-            int cnt = 0;
-            // MASK: the lane's 4 rows are bits (it & 1) * 16 + (lane >> 4) * 4 + r of the word. The
-            // empty asm keeps the shift and the bit tests here, out of the tiles without candidates
-            // (retrieval.hip)
-            uint32_t mbits = 0xfu;
-            if constexpr (MASK) {
-              uint32_t mw = mword;
-              asm volatile("" : "+v"(mw));
-              mbits = mw >> ((it & 1) * 16 + (lane >> 4) * 4);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              pass[r] = acc[r] > thr[qt] && nb + r < n_end;
-              if constexpr (MASK) pass[r] = pass[r] && ((mbits >> r) & 1u);
-              cnt += pass[r] ? 1 : 0;
-            }
-            const int c16 = __shfl_xor(cnt, 16, 64);
-            const int c32 = __shfl_xor(cnt + c16, 32, 64);
-            const int tot = cnt + c16 + c32;
-            const int ex = ((lane & 16) ? c16 : 0) + ((lane & 32) ? c32 : 0);
-            int base = w.ccnt[q];
-            // first merge the buffers they do not fit in
-            u64 need = __ballot(lane < 16 && base + tot > TK_CB);
-            const bool merged = need != 0ull;
-            while (need) {
-              const int qi = qt * 16 + __builtin_ctzll(need);
-              need &= need - 1;
-              if constexpr (FILT) {
-                if (wave_excl) {
-                  const int mq = __builtin_amdgcn_readfirstlane(qid[qi]);
-                  if (topk_drop_excluded(w, qi, excl_values, a.excl_offsets + mq, lane) == 0)
-                    continue;  // nothing left to merge, and the buffer is empty
-                }
-              }
-              topk_merge_query(w, qi, a.ws + (int64_t)(p_wave + qi) * k, k, lane);
-            }
-            if (merged) base = w.ccnt[q];
-            int slot = base + ex;
-            // the key carries the item's original index
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (pass[r]) w.cbuf[q * TK_CB + slot++] = make_key(acc[r], a.labels[nb + r]);
-            if (lane < 16 && tot > 0) w.ccnt[q] = base + tot;
-            lds_wave_sync();
-            if (merged) thr[qt] = w.thrs[q];
-          }
-        }
-      }
-    }
-    if (c + 1 < nchunks) store_chunk(buf ^ 1);
-    __syncthreads();
-  }
-
-  // flush the buffers; pad the lists shorter than k
-#pragma unroll 1
-  for (int q = 0; q < pw; ++q) {
-    u64* gl = a.ws + (int64_t)(p_wave + q) * k;
-    if constexpr (FILT) {
-      if (w.ccnt[q] > 0 && wave_excl) {
-        const int mq = __builtin_amdgcn_readfirstlane(qid[q]);
-        if (mq >= 0) topk_drop_excluded(w, q, excl_values, a.excl_offsets + mq, lane);
-      }
-    }
-    if (w.ccnt[q] > 0) topk_merge_query(w, q, gl, k, lane);
-    for (int i = w.lcnt[q] + lane; i < k; i += 64) gl[i] = 0ull;
-  }
+  IvfSrc<KS, MASK> s{a, qid, pw, a.ws + (int64_t)p_wave * a.k, n_beg, n_beg + len, (len + TK_IC - 1) / TK_IC,
+                     wave_excl, excl_values, mask_p, tid & (ScanShape<KS>::MW - 1), (len - 1) >> 5};
+  topk_scan_body<KS, BIAS, FILT, MASK>(s);
 }
 
 // ids / scores [M][k] from the sorted lists of each query's pairs: one wave per query, lane j walks
-// the list of the query's probe column j (no list where the probe was no probe); k rounds of a
-// wave-wide max over the heads. The lists of distinct probes hold distinct items, so keys are distinct
+// the list of the query's probe column j (no list where the probe was no probe). The lists of
+// distinct probes hold distinct items, so keys are distinct
 __global__ void __launch_bounds__(TK_THREADS) ivf_merge_kernel(const u64* __restrict__ ws,
                                                                const int32_t* __restrict__ slot_of, int64_t M,
                                                                int nprobe, int k, int64_t* __restrict__ ids,
@@ -428,43 +296,15 @@ __global__ void __launch_bounds__(TK_THREADS) ivf_merge_kernel(const u64* __rest
   const int64_t m = (int64_t)blockIdx.x * TK_WAVES + (threadIdx.x >> 6);
   if (m >= M) return;
   const int slot = lane < nprobe ? slot_of[m * nprobe + lane] : -1;
-  const u64* base = ws + (int64_t)(slot >= 0 ? slot : 0) * k;
-  int p = 0;
-  u64 head = slot >= 0 ? base[0] : 0ull;
-  for (int i = 0; i < k; ++i) {
-    u64 mx = head;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const u64 t = __shfl_xor(mx, o, 64);
-      mx = t > mx ? t : mx;
-    }
-    if (lane == 0) {
-      ids[m * k + i] = mx ? (int64_t)key_index(mx) : (int64_t)-1;
-      scores[m * k + i] = mx ? key_score(mx) : -std::numeric_limits<float>::infinity();
-    }
-    if (mx != 0ull && head == mx) {
-      ++p;
-      head = p < k ? base[p] : 0ull;
-    }
-  }
-}
-
-template <int KS, bool FILT, bool MASK>
-static void ivf_launch(const IvfMaskArgs& a, unsigned blocks, hipStream_t st) {
-  if (a.bias)
-    hipLaunchKernelGGL((ivf_scan_kernel<KS, true, FILT, MASK>), dim3(blocks), dim3(TK_THREADS), 0, st, a);
-  else
-    hipLaunchKernelGGL((ivf_scan_kernel<KS, false, FILT, MASK>), dim3(blocks), dim3(TK_THREADS), 0, st, a);
+  topk_merge_lists(ws + (int64_t)(slot >= 0 ? slot : 0) * k, slot >= 0, m, k, ids, scores);
 }
 
 template <bool FILT, bool MASK>
-static void ivf_launch_e(const IvfMaskArgs& a, int E, unsigned blocks, hipStream_t st) {
-  switch (E / 32) {
-    case 1: ivf_launch<1, FILT, MASK>(a, blocks, st); break;
-    case 2: ivf_launch<2, FILT, MASK>(a, blocks, st); break;
-    case 3: ivf_launch<3, FILT, MASK>(a, blocks, st); break;
-    default: ivf_launch<4, FILT, MASK>(a, blocks, st); break;
-  }
+static void ivf_launch(const IvfMaskArgs& a, int E, unsigned blocks, hipStream_t st) {
+  topk_dispatch(E, a.bias != nullptr, [&](auto ks, auto bias) {
+    hipLaunchKernelGGL((ivf_scan_kernel<decltype(ks)::value, decltype(bias)::value, FILT, MASK>), dim3(blocks),
+                       dim3(TK_THREADS), 0, st, a);
+  });
 }
 
 static const char* ivf_check(int64_t M, int nprobe, int k, int64_t L) {
@@ -652,14 +492,14 @@ static int ivf_scan_impl(const char* name, bool masked, const void* queries, int
   const unsigned blocks = (unsigned)(ceil_div(PN, TK_QB) + std::min<int64_t>(L, PN));
   if (masked) {
     if (excl_offsets)
-      ivf_launch_e<true, true>(a, E, blocks, st);
+      ivf_launch<true, true>(a, E, blocks, st);
     else
-      ivf_launch_e<false, true>(a, E, blocks, st);
+      ivf_launch<false, true>(a, E, blocks, st);
   } else {
     if (excl_offsets)
-      ivf_launch_e<true, false>(a, E, blocks, st);
+      ivf_launch<true, false>(a, E, blocks, st);
     else
-      ivf_launch_e<false, false>(a, E, blocks, st);
+      ivf_launch<false, false>(a, E, blocks, st);
   }
   if (int rc = check_launch((fn + "list scan").c_str())) return rc;
   hipLaunchKernelGGL(ivf_merge_kernel, dim3((unsigned)ceil_div(M, TK_WAVES)), dim3(TK_THREADS), 0, st, w.lists,

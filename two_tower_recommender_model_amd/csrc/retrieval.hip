@@ -1,43 +1,18 @@
-// Exact top-k maximum-inner-product retrieval on gfx950 (tt_topk_mips): the scores of a query
-// tile against a stream of items on bf16 MFMA (v_mfma_f32_16x16x32_bf16, fp32 accumulate) with the
-// selection fused behind it, so a score leaves the registers only when it is a candidate.
-// Replaces the vector-index query loop of 04_evaluate_retrieval.py:131-153.
+// Exact top-k maximum-inner-product retrieval on gfx950 (tt_topk_mips): the shared scan
+// (topk_scan.h: the scores of a query tile against a stream of items on bf16 MFMA, the selection
+// fused behind them) over the whole item table. Replaces the vector-index query loop of
+// 04_evaluate_retrieval.py:131-153.
 //
-//   grid = query tiles (128 queries) x item splits; 256 threads, each wave owns 32 queries
-//   (2 tiles of 16) whose fragments stay in registers as the MFMA's B operand; the workgroup stages
-//   chunks of 128 items (64 when E > 64) of its split through LDS (converted to bf16 once,
-//   double-buffered, the next chunk's global loads in flight during the compute, one barrier per
-//   chunk) as the A operand. Accumulator layout: lane l holds query l & 15 against items
-//   (l >> 4) * 4 + r, so the running k-th-best threshold of a tile is ONE register per lane and the
-//   filter is max3 + max + compare per 4 scores.
+//   grid = query tiles (128 queries) x item splits; a workgroup streams its split's items (f32 or
+//   bf16, converted to bf16 once on the way into LDS) past its query tile and leaves each query's
+//   sorted partial list in the workspace ([S][M][k]). A second kernel merges the S splits' lists of
+//   a query (one lane per split).
 //
-// Every entry (score, index) is one 64-bit key whose unsigned order is the total order "higher
-// score first, equal scores by lower index": key = orderable(score) << 32 | ~index. A score that
-// beats its query's threshold is appended to the query's candidate buffer in LDS (32 keys); a
-// buffer that the next tile's candidates do not fit in is merged into the query's sorted partial
-// list (k keys, in the workspace, read and written by the owning wave only) by rank counting,
-// which raises the threshold. Items are streamed in ascending index order, so "score > threshold"
-// (strict) loses nothing: an equal score met later has a higher index than everything in the list.
-// A second kernel merges the S splits' sorted lists of a query (one lane per split, k rounds of a
-// wave-wide max).
-//
-// The score of a pair is the MFMA chain over E in ascending k-steps from a zero accumulator, then
-// + bias: a function of the two rows' bf16 values and bias[n] only, so the result (unique under the
-// total order) is bit-identical across runs, M, N and split counts.
-//
-// tt_topk_mips_filtered runs the FILT instantiations of the same kernel: the top k over each query's
-// ELIGIBLE items. The item mask shared by all queries (a bit per item) is staged per chunk beside the
-// bias and decides, with the threshold, what becomes a candidate. A query's exclusion list (ascending
-// item indices) is tested where it is cheap: not per candidate, but when the query's candidate
-// buffer is about to be merged into its list (topk_drop_excluded: one lane per buffered key, a binary
-// search each). Thresholds rise only in a merge and the final flush merges too, so an excluded key
-// never raises a threshold, never enters a list and never displaces an eligible item; all it costs
-// is its place in the buffer until the next merge. The unfiltered instantiations are unchanged.
+// tt_topk_mips_filtered runs the FILT instantiations: the top k over each query's ELIGIBLE items,
+// with the item mask (`allow`, a bit per item) as the scan's row mask and the queries' exclusion
+// lists. The unfiltered instantiations carry neither.
 #include "tt_common.h"
-#include "topk_common.h"
-
-#include <limits>
-#include <type_traits>
+#include "topk_scan.h"
 
 namespace tt {
 
@@ -59,86 +34,34 @@ struct TopkFiltArgs : TopkArgs {
   const int64_t* excl_offsets;
 };
 
-template <int KS, bool BIAS, bool FILT>
-__global__ void __launch_bounds__(TK_THREADS, 2)
-    topk_mips_kernel(const std::conditional_t<FILT, TopkFiltArgs, TopkArgs> a) {
-  constexpr int E = KS * 32, STRIDE = E + 8, GPR = E / 8;  // GPR: 8-element groups per item row
-  constexpr int TK_IC = tk_chunk(E);
-  constexpr int GPT = TK_IC * GPR / TK_THREADS;             // groups per thread
-  __shared__ __attribute__((aligned(16))) __bf16 items[2][TK_IC * STRIDE];
-  // FILT: the chunk's TK_IC / 32 mask words follow its bias
-  __shared__ __attribute__((aligned(16))) float bias_s[2][TK_IC + (FILT ? TK_IC / 32 : 0)];
-  __shared__ u64 cbuf_s[TK_WAVES][TK_QW * TK_CB];
-  __shared__ u64 lscr_s[TK_WAVES][TT_TOPK_MAX_K];
-  __shared__ int ccnt_s[TK_WAVES][TK_QW];
-  __shared__ int lcnt_s[TK_WAVES][TK_QW];
-  __shared__ float thrs_s[TK_WAVES][TK_QW];
-
-  // workgroups of one item split are consecutive in the logical order, and an XCD runs a contiguous
-  // part of it: the split's item stream is read from HBM once and shared through that XCD's L2
-  const int logical = xcd_remap((int)blockIdx.x, (int)gridDim.x);
-  const int split = logical / a.qtiles, qtile = logical - split * a.qtiles;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int64_t n_beg = (int64_t)split * a.per;
-  const int64_t n_end = n_beg + a.per < a.N ? n_beg + a.per : a.N;
-  const int nchunks = n_end > n_beg ? (int)((n_end - n_beg + TK_IC - 1) / TK_IC) : 0;
-  const int64_t m_wave = (int64_t)qtile * TK_QB + wid * TK_QW;
-  const int k = a.k;
-
-  const WaveSel w{cbuf_s[wid], lscr_s[wid], ccnt_s[wid], lcnt_s[wid], thrs_s[wid]};
-  for (int i = lane; i < TK_QW * TK_CB; i += 64) w.cbuf[i] = 0ull;
-  if (lane < TK_QW) {
-    w.ccnt[lane] = 0;
-    w.lcnt[lane] = 0;
-    w.thrs[lane] = m_wave + lane < a.M ? -std::numeric_limits<float>::infinity() : std::numeric_limits<float>::infinity();
-  }
-  // FILT: does any of the wave's queries have a non-empty exclusion segment (offsets never decrease)?
-  // Where none has, the merges go as in the unfiltered kernel, without the look at the offsets
-  bool wave_excl = false;
-  if constexpr (FILT) {
-    if (a.excl_offsets && m_wave < a.M) {
-      const int64_t m_last = m_wave + TK_QW < a.M ? m_wave + TK_QW : a.M;
-      wave_excl = __builtin_amdgcn_readfirstlane((int)(a.excl_offsets[m_last] > a.excl_offsets[m_wave])) != 0;
-    }
-  }
-
-  // the wave's queries as B operands: lane l holds query (l & 15), k = 32 ks + 8 (l >> 4) + j
-  bf16x8 qf[2][KS];
-  float thr[2];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int64_t m = m_wave + qt * 16 + (lane & 15);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      bf16x8 f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float x = 0.f;
-        if (m < a.M) {
-          const int64_t o = m * a.ldq + ks * 32 + (lane >> 4) * 8 + j;
-          x = a.q_bf16 ? __uint_as_float(((uint32_t) reinterpret_cast<const unsigned short*>(a.q)[o]) << 16)
-                       : reinterpret_cast<const float*>(a.q)[o];
-        }
-        f[j] = (__bf16)x;
-      }
-      qf[qt][ks] = f;
-    }
-    thr[qt] = m < a.M ? -std::numeric_limits<float>::infinity() : std::numeric_limits<float>::infinity();
-  }
-  wave_sync();
-
+// a workgroup's work unit for the shared scan (topk_scan.h): a query tile's wave against one split
+template <int KS, bool FILT>
+struct ExactSrc {
+  using Sh = ScanShape<KS>;
+  const std::conditional_t<FILT, TopkFiltArgs, TopkArgs>& a;
+  int64_t m_wave;  // the wave's queries: m_wave + q, while < M
+  u64* lists;
+  int64_t n_beg, n_end;
+  int nchunks;
+  bool wave_excl;
+  const int32_t* excl_values;
+  bool raw_bf16;  // bf16 rows that 16-byte loads can fetch: staged as they are
   // staging: thread t holds 8-element groups g = t + TK_THREADS i of the chunk: item row g / GPR
-  const bool raw_bf16 = a.c_bf16 && a.c_vec;
-  f32x4 rawf[GPT][2];
-  bf16x8 rawb[GPT];
-  float rawbias = 0.f;
-  uint32_t rawmask = 0u;
-  auto load_chunk = [&](int c) {
-    const int64_t n0 = n_beg + (int64_t)c * TK_IC;
+  f32x4 rawf[Sh::GPT][2];
+  bf16x8 rawb[Sh::GPT];
+  uint32_t rawmask;
+
+  __device__ __forceinline__ bool computes() const { return true; }
+  __device__ __forceinline__ int64_t query(int q) const { return m_wave + q < a.M ? m_wave + q : -1; }
+  __device__ __forceinline__ int index(int64_t n) const { return (int)n; }
+  __device__ __forceinline__ bool has_list(int q) const { return m_wave + q < a.M; }
+  __device__ __forceinline__ const int64_t* excl(int q) const { return a.excl_offsets + m_wave + q; }
+
+  __device__ __forceinline__ void load_rows(int64_t n0, int tid) {
 #pragma unroll
-    for (int i = 0; i < GPT; ++i) {
+    for (int i = 0; i < Sh::GPT; ++i) {
       const int g = tid + TK_THREADS * i;
-      const int row = g / GPR, kc = (g - row * GPR) * 8;
+      const int row = g / Sh::GPR, kc = (g - row * Sh::GPR) * 8;
       const int64_t n = n0 + row;
       if (raw_bf16) {
         bf16x8 z;
@@ -162,20 +85,12 @@ __global__ void __launch_bounds__(TK_THREADS, 2)
         }
       }
     }
-    if (BIAS && tid < TK_IC) rawbias = n0 + tid < n_end ? a.bias[n0 + tid] : 0.f;
-    if constexpr (FILT) {
-      // n0 is a multiple of the chunk, the chunk of 32: the chunk's words are whole
-      if (tid < TK_IC / 32) {
-        const int64_t wd = (n0 >> 5) + tid;
-        rawmask = !a.allow ? 0xffffffffu : wd < ((a.N + 31) >> 5) ? a.allow[wd] : 0u;
-      }
-    }
-  };
-  auto store_chunk = [&](int buf) {
+  }
+  __device__ __forceinline__ void store_rows(__bf16* buf, int tid) const {
 #pragma unroll
-    for (int i = 0; i < GPT; ++i) {
+    for (int i = 0; i < Sh::GPT; ++i) {
       const int g = tid + TK_THREADS * i;
-      const int row = g / GPR, kc = (g - row * GPR) * 8;
+      const int row = g / Sh::GPR, kc = (g - row * Sh::GPR) * 8;
       bf16x8 o;
       if (raw_bf16) {
         o = rawb[i];
@@ -183,137 +98,62 @@ __global__ void __launch_bounds__(TK_THREADS, 2)
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = (__bf16)rawf[i][j >> 2][j & 3];  // round-to-nearest-even
       }
-      *reinterpret_cast<bf16x8*>(&items[buf][row * STRIDE + kc]) = o;
+      *reinterpret_cast<bf16x8*>(&buf[row * Sh::STRIDE + kc]) = o;
     }
-    if (BIAS && tid < TK_IC) bias_s[buf][tid] = rawbias;
-    if constexpr (FILT) {
-      if (tid < TK_IC / 32) *reinterpret_cast<uint32_t*>(&bias_s[buf][TK_IC + tid]) = rawmask;
-    }
-  };
-
-  if (nchunks > 0) {
-    load_chunk(0);
-    store_chunk(0);
   }
-  __syncthreads();
-
-  for (int c = 0; c < nchunks; ++c) {
-    const int buf = c & 1;
-    if (c + 1 < nchunks) load_chunk(c + 1);
-    const int64_t n0 = n_beg + (int64_t)c * TK_IC;
-#pragma unroll 1
-    for (int it = 0; it < TK_IC / 16; ++it) {
-      bf16x8 af[KS];
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-        af[ks] = *reinterpret_cast<const bf16x8*>(&items[buf][(it * 16 + (lane & 15)) * STRIDE + ks * 32 + (lane >> 4) * 8]);
-      f32x4 bv = (f32x4)(0.f);
-      if (BIAS) bv = *reinterpret_cast<const f32x4*>(&bias_s[buf][it * 16 + (lane >> 4) * 4]);
-      // FILT: the chunk's mask word it >> 1, read with the tile's other LDS reads: not one more
-      // latency inside the candidate branch
-      uint32_t mword = 0u;
-      if constexpr (FILT) mword = *reinterpret_cast<const uint32_t*>(&bias_s[buf][TK_IC + (it >> 1)]);
-#pragma unroll
-      for (int qt = 0; qt < 2; ++qt) {
-        f32x4 acc = (f32x4)(0.f);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks], qf[qt][ks], acc, 0, 0, 0);
-        if (BIAS) acc += bv;
-        const float mx = fmaxf(fmaxf(acc[0], acc[1]), fmaxf(acc[2], acc[3]));
-        if (__ballot(mx > thr[qt]) != 0ull) {
-          // candidates of this tile, decided against the threshold as it stood before the tile
-          const int q = qt * 16 + (lane & 15);
-          const int64_t nb = n0 + it * 16 + (lane >> 4) * 4;
-          bool pass[4];
-          int cnt = 0;
-          // FILT: the lane's 4 items are bits (it & 1) * 16 + (lane >> 4) * 4 + r of the word. The
-          // empty asm keeps the shift and the bit tests here: the compiler otherwise hoists them
-          // (9 VALU instructions) into every tile, candidates or not
-          uint32_t mbits = 0xfu;
-          if constexpr (FILT) {
-            uint32_t mw = mword;
-            asm volatile("" : "+v"(mw));
-            mbits = mw >> ((it & 1) * 16 + (lane >> 4) * 4);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            pass[r] = acc[r] > thr[qt] && nb + r < n_end;
-            if constexpr (FILT) pass[r] = pass[r] && ((mbits >> r) & 1u);
-            cnt += pass[r] ? 1 : 0;
-          }
-          // the tile's candidates per query (its 4 lanes l, l ^ 16, l ^ 32, l ^ 48: at most 16) and
-          // this lane's place among them
-          const int c16 = __shfl_xor(cnt, 16, 64);
-          const int c32 = __shfl_xor(cnt + c16, 32, 64);
-          const int tot = cnt + c16 + c32;
-          const int ex = ((lane & 16) ? c16 : 0) + ((lane & 32) ? c32 : 0);
-          int base = w.ccnt[q];
-          // first merge the buffers they do not fit in
-          u64 need = __ballot(lane < 16 && base + tot > TK_CB);
-          const bool merged = need != 0ull;
-          while (need) {
-            const int qi = qt * 16 + __builtin_ctzll(need);
-            need &= need - 1;
-            if constexpr (FILT) {
-              if (wave_excl && topk_drop_excluded(w, qi, a.excl_values, a.excl_offsets + m_wave + qi, lane) == 0)
-                continue;  // nothing left to merge, and the buffer is empty
-            }
-            topk_merge_query(w, qi, a.ws + ((int64_t)split * a.M + m_wave + qi) * k, k, lane);
-          }
-          if (merged) base = w.ccnt[q];
-          int slot = base + ex;
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (pass[r]) w.cbuf[q * TK_CB + slot++] = make_key(acc[r], (int)(nb + r));
-          if (lane < 16 && tot > 0) w.ccnt[q] = base + tot;
-          lds_wave_sync();
-          if (merged) thr[qt] = w.thrs[q];
-        }
-      }
+  // the chunk's words of `allow` (all ones where it is NULL), one thread per word. n0 is a multiple
+  // of the chunk, the chunk of 32: the words are whole; those past the N items count as zero
+  __device__ __forceinline__ void load_mask(int, int64_t n0, int tid) {
+    if (tid < Sh::MW) {
+      const int64_t wd = (n0 >> 5) + tid;
+      rawmask = !a.allow ? 0xffffffffu : wd < ((a.N + 31) >> 5) ? a.allow[wd] : 0u;
     }
-    if (c + 1 < nchunks) store_chunk(buf ^ 1);
-    __syncthreads();
   }
+  __device__ __forceinline__ void store_mask(uint32_t* words, int tid) const {
+    if (tid < Sh::MW) words[tid] = rawmask;
+  }
+};
 
-  // flush the buffers; pad the lists shorter than k
-#pragma unroll 1
-  for (int q = 0; q < TK_QW; ++q) {
-    if (m_wave + q >= a.M) break;
-    u64* gl = a.ws + ((int64_t)split * a.M + m_wave + q) * k;
-    if constexpr (FILT) {
-      if (w.ccnt[q] > 0 && wave_excl) topk_drop_excluded(w, q, a.excl_values, a.excl_offsets + m_wave + q, lane);
+template <int KS, bool BIAS, bool FILT>
+__global__ void __launch_bounds__(TK_THREADS, 2)
+    topk_mips_kernel(const std::conditional_t<FILT, TopkFiltArgs, TopkArgs> a) {
+  constexpr int TK_IC = ScanShape<KS>::IC;
+  // workgroups of one item split are consecutive in the logical order, and an XCD runs a contiguous
+  // part of it: the split's item stream is read from HBM once and shared through that XCD's L2
+  const int logical = xcd_remap((int)blockIdx.x, (int)gridDim.x);
+  const int split = logical / a.qtiles, qtile = logical - split * a.qtiles;
+  const int64_t n_beg = (int64_t)split * a.per;
+  const int64_t n_end = n_beg + a.per < a.N ? n_beg + a.per : a.N;
+  const int nchunks = n_end > n_beg ? (int)((n_end - n_beg + TK_IC - 1) / TK_IC) : 0;
+  const int64_t m_wave = (int64_t)qtile * TK_QB + (threadIdx.x >> 6) * TK_QW;
+  // FILT: does any of the wave's queries have a non-empty exclusion segment (offsets never decrease)?
+  // Where none has, the merges go as in the unfiltered kernel, without the look at the offsets
+  bool wave_excl = false;
+  const int32_t* excl_values = nullptr;
+  if constexpr (FILT) {
+    excl_values = a.excl_values;
+    if (a.excl_offsets && m_wave < a.M) {
+      const int64_t m_last = m_wave + TK_QW < a.M ? m_wave + TK_QW : a.M;
+      wave_excl = __builtin_amdgcn_readfirstlane((int)(a.excl_offsets[m_last] > a.excl_offsets[m_wave])) != 0;
     }
-    if (w.ccnt[q] > 0) topk_merge_query(w, q, gl, k, lane);
-    for (int i = w.lcnt[q] + lane; i < k; i += 64) gl[i] = 0ull;
   }
+  // the wave's lists in [S][M][k]. FILT: the address is held in vector registers (as m_wave is): left
+  // to itself the compiler keeps its scalar part in 5 more scalar registers across the scan, which
+  // these instantiations do not have
+  u64* lists = a.ws + ((int64_t)split * a.M + m_wave) * a.k;
+  if constexpr (FILT) asm volatile("" : "+v"(lists));
+  ExactSrc<KS, FILT> s{a, m_wave, lists, n_beg, n_end, nchunks, wave_excl, excl_values, a.c_bf16 && a.c_vec};
+  topk_scan_body<KS, BIAS, FILT, FILT>(s);
 }
 
 // ids / scores [M][k] from the S sorted lists of each query: one wave per query, lane j walks
-// split j's list; k rounds of a wave-wide max over the heads
+// split j's list
 __global__ void __launch_bounds__(TK_THREADS) topk_merge_kernel(const u64* __restrict__ ws, int64_t M, int k, int S,
                                                                 int64_t* __restrict__ ids, float* __restrict__ scores) {
   const int lane = threadIdx.x & 63;
   const int64_t m = (int64_t)blockIdx.x * TK_WAVES + (threadIdx.x >> 6);
   if (m >= M) return;
-  const u64* base = ws + ((int64_t)(lane < S ? lane : 0) * M + m) * k;
-  int p = 0;
-  u64 head = lane < S ? base[0] : 0ull;
-  for (int i = 0; i < k; ++i) {
-    u64 mx = head;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const u64 t = __shfl_xor(mx, o, 64);
-      mx = t > mx ? t : mx;
-    }
-    if (lane == 0) {
-      ids[m * k + i] = mx ? (int64_t)key_index(mx) : (int64_t)-1;
-      scores[m * k + i] = mx ? key_score(mx) : -std::numeric_limits<float>::infinity();
-    }
-    if (mx != 0ull && head == mx) {
-      ++p;
-      head = p < k ? base[p] : 0ull;
-    }
-  }
+  topk_merge_lists(ws + ((int64_t)(lane < S ? lane : 0) * M + m) * k, lane < S, m, k, ids, scores);
 }
 
 static int topk_auto_splits(int64_t M, int64_t N) {
@@ -334,23 +174,13 @@ static const char* topk_check(int64_t M, int64_t N, int k, int splits) {
   return nullptr;
 }
 
-template <int KS, bool FILT>
-static void topk_launch(const TopkFiltArgs& a, int blocks, hipStream_t st) {
-  const std::conditional_t<FILT, TopkFiltArgs, TopkArgs>& ka = a;
-  if (a.bias)
-    hipLaunchKernelGGL((topk_mips_kernel<KS, true, FILT>), dim3(blocks), dim3(TK_THREADS), 0, st, ka);
-  else
-    hipLaunchKernelGGL((topk_mips_kernel<KS, false, FILT>), dim3(blocks), dim3(TK_THREADS), 0, st, ka);
-}
-
 template <bool FILT>
-static void topk_launch_e(const TopkFiltArgs& a, int E, int blocks, hipStream_t st) {
-  switch (E / 32) {
-    case 1: topk_launch<1, FILT>(a, blocks, st); break;
-    case 2: topk_launch<2, FILT>(a, blocks, st); break;
-    case 3: topk_launch<3, FILT>(a, blocks, st); break;
-    default: topk_launch<4, FILT>(a, blocks, st); break;
-  }
+static void topk_launch(const TopkFiltArgs& a, int E, int blocks, hipStream_t st) {
+  const std::conditional_t<FILT, TopkFiltArgs, TopkArgs>& ka = a;
+  topk_dispatch(E, a.bias != nullptr, [&](auto ks, auto bias) {
+    hipLaunchKernelGGL((topk_mips_kernel<decltype(ks)::value, decltype(bias)::value, FILT>), dim3(blocks),
+                       dim3(TK_THREADS), 0, st, ka);
+  });
 }
 
 // both entry points: `fn_name` prefixes the messages, `fn_merge` names the second launch; the FILT
@@ -397,9 +227,9 @@ static int topk_run(const char* fn_name, const char* fn_merge, const void* queri
   const int blocks = (int)(qtiles * S);
   hipStream_t st = as_stream(stream);
   if (allow || excl_offsets)
-    topk_launch_e<true>(a, E, blocks, st);
+    topk_launch<true>(a, E, blocks, st);
   else
-    topk_launch_e<false>(a, E, blocks, st);
+    topk_launch<false>(a, E, blocks, st);
   if (int rc = check_launch(fn_name)) return rc;
   hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)ceil_div(M, TK_WAVES)), dim3(TK_THREADS), 0, st, a.ws, M, k, S,
                      ids, scores);
