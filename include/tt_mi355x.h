@@ -726,9 +726,11 @@ int tt_ivf_scan_masked(const void* queries, int q_dtype, int64_t ldq, int64_t M,
 /* The centroid update of the index's k-means (ABI 4 addition): out[l, :] = the mean of
  * rows[order[i], :] over i in [seg_offsets[l], seg_offsets[l + 1]) for each of L segments; rows
  * [n, E] fp32 or bf16 with row stride ld, order [n] int64 (row indices; one outside [0, n) adds
- * nothing), seg_offsets [L + 1] int64 non-decreasing (clamped to [0, n]), out [L, E] fp32. Every
+ * nothing), seg_offsets [L + 1] int64 non-decreasing (clamped to [0, n]), out [L, E] fp32. The
+ * divisor is the CLAMPED segment length min(seg_offsets[l + 1], n) - max(seg_offsets[l], 0): an
+ * order entry outside [0, n) adds nothing to the sum and still counts in the divisor. Every
  * element is summed in fp32 in one fixed order (no atomics), so the result is bit-identical from run
- * to run; an empty segment leaves its out row untouched. Limits: 1 <= E <= 4096, ld >= E, n >= 1,
+ * to run; a segment that is empty after clamping leaves its out row untouched. Limits: 1 <= E <= 4096, ld >= E, n >= 1,
  * 1 <= L <= 2^20, no NULL pointer. */
 int tt_ivf_segment_mean(const void* rows, int dtype, int64_t ld, int64_t n, int E, const int64_t* order,
                         const int64_t* seg_offsets, int64_t L, float* out, void* stream);

@@ -22,6 +22,7 @@ import torch
 from . import ops
 
 LIST_ALIGN = 128  # every list begins at a multiple of the scan's largest chunk
+MAX_NPROBE = 64   # tt_ivf_scan's limit: one lane of the merge per probed list
 
 
 def _l2_bias(x: torch.Tensor) -> torch.Tensor:
@@ -136,12 +137,13 @@ class IVFIndex:
         return cls(metric=d["metric"], N=d["N"], **t)
 
     def probes(self, user_emb: torch.Tensor, nprobe: int) -> torch.Tensor:
-        """The coarse step: int32 [M, min(nprobe, L)], each query's nearest centroids (by L2 for
-        metric "l2", by inner product for "dot"). On a restricted view only lists that hold an
+        """The coarse step: int32 [M, min(nprobe, 64, L)], each query's nearest centroids (by L2 for
+        metric "l2", by inner product for "dot"). ``nprobe`` is clamped to [1, min(64, L)]: 64 is
+        the most lists tt_ivf_scan takes per query. On a restricted view only lists that hold an
         eligible item count (the exact filtered kernel with ``list_allow`` as the item mask); where
         fewer than nprobe such lists exist the tail columns are -1, which the scan takes for "no
         probe"."""
-        nprobe = max(1, min(int(nprobe), self.nlist))
+        nprobe = max(1, min(int(nprobe), MAX_NPROBE, self.nlist))
         ids, _ = ops.topk_mips(user_emb, self.centroids, nprobe,
                                bias=self.centroid_bias if self.metric == "l2" else None, allow=self.list_allow)
         return ids.to(torch.int32)

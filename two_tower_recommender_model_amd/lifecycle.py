@@ -215,7 +215,7 @@ def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metri
 
     ``index`` (ivf.IVFIndex over the same ``item_emb``, built for the same ``metric``): the
     approximate query instead, each user against its ``nprobe`` nearest lists only
-    (IVFIndex.search); ids, scores and the seen lists as above, ``item_emb`` and ``bias`` are not
+    (IVFIndex.search; ``nprobe`` is clamped to min(nprobe, 64, the index's lists)); ids, scores and the seen lists as above, ``item_emb`` and ``bias`` are not
     read (the index holds its own copy). An item mask goes to the index itself, as the reference's
     ``filters=`` does: pass ``index=index.restricted(allow)`` (the coarse step then counts only lists
     with an eligible item, the fine step is the masked list scan); ``allow=`` beside ``index=`` is
