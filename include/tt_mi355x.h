@@ -44,6 +44,7 @@
  *                                 (exact top-k by inner product over the exported item embeddings)
  *   tt_topk_mips_filtered      <- the same query with the index's `filters=` (04:100, an item mask
  *                                 shared by all queries) and each user's seen items excluded
+ *   tt_topk_mips_large         <- the same query at k in the thousands (04:91 asks for k = 5000)
  *   tt_launch (a launch plan)  <- the same backward work with several roles in one launch: the
  *                                 weight gradients beside the embedding update / next-batch insert /
  *                                 shard route and gather ("launch plans" below)
@@ -645,6 +646,41 @@ int tt_topk_mips_filtered(const void* queries, int q_dtype, int64_t ldq, const v
                           const float* bias, int64_t M, int64_t N, int E, int k, int splits,
                           const uint32_t* allow, const int32_t* excl_values, const int64_t* excl_offsets,
                           int64_t* ids, float* scores, void* workspace, size_t ws_bytes, void* stream);
+
+/* tt_topk_mips_filtered for k up to 8192 (ABI 4 addition; not part of tt_num_entry_points()): candidate
+ * generation for a ranker, thousands of items per user (the reference's first search cell asks its
+ * index for k = 5000, 04_evaluate_retrieval.py:91). One entry point: arguments, operand types,
+ * strides, rounding, `allow`, `excl_values` / `excl_offsets` and `splits` are
+ * tt_topk_mips_filtered's; all three filter pointers NULL is the unfiltered query.
+ * CONTRACT: exactly tt_topk_mips_filtered's. A pair's score is the same bits (the bf16 MFMA chain
+ * over E in ascending k-steps from a zero accumulator, then + bias); the total order is "higher
+ * score first, equal scores by lower index"; ids are int64 row indices; the tail is id -1 / score
+ * -inf where fewer than k items are eligible; a denied item is never returned and never raises a
+ * threshold. The result is therefore unique, bit-identical across runs and split counts; for k <=
+ * TT_TOPK_MAX_K it is bit-identical to tt_topk_mips / tt_topk_mips_filtered, and for any k its first
+ * 256 columns are their k = 256 result.
+ * Selection: instead of a sorted list, every (split, query) keeps an unsorted pool of 2 k + 32 keys
+ * in the workspace, appended to by the owning wave and pruned, when full, by a radix select of its
+ * k-th key (8-bit digits, a 256-bin histogram per wave in LDS) and a compaction in place. Two
+ * launches on `stream`: the fused score + select over (query tiles x item splits), and the merge
+ * (one workgroup per query: select over the splits' k keys each, sort, ids / scores). No allocation,
+ * no synchronisation, never a score matrix. `splits` = 0 lets the library choose (tt_topk_mips'
+ * occupancy aim, but a split holds at least 4 k items).
+ * Workspace: tt_topk_mips_large_workspace_bytes = S * M * (2 k + 32) * 8 bytes with S the split
+ * count (`splits`, or the library's choice for M, N, k when 0): independent of N at fixed S. It need
+ * not be initialised.
+ * Limits (TT_EINVAL otherwise, before any launch, the message starting "tt_topk_mips_large"): E a
+ * multiple of 32 in [32, 128]; 1 <= k <= TT_TOPK_LARGE_MAX_K (small k is accepted so that the two
+ * selections can be compared); 1 <= M <= 2^30; 1 <= N < 2^31; splits 0 or in [1, 64]; dtypes TT_F32 /
+ * TT_BF16; ldq, ldc >= E; queries, items, ids, scores, workspace not NULL; excl_values and
+ * excl_offsets both NULL or both given; ws_bytes >= the workspace query, which returns 0 for
+ * arguments outside the limits. Scores must be finite, as for tt_topk_mips. */
+#define TT_TOPK_LARGE_MAX_K 8192
+size_t tt_topk_mips_large_workspace_bytes(int64_t M, int64_t N, int k, int splits);
+int tt_topk_mips_large(const void* queries, int q_dtype, int64_t ldq, const void* items, int c_dtype, int64_t ldc,
+                       const float* bias, int64_t M, int64_t N, int E, int k, int splits, const uint32_t* allow,
+                       const int32_t* excl_values, const int64_t* excl_offsets, int64_t* ids, float* scores,
+                       void* workspace, size_t ws_bytes, void* stream);
 
 /* IVF (inverted-file) approximate top-k (ABI 4 addition): the fine step of the approximate vector
  * index that 04_evaluate_retrieval.py:112-153 queries. The index holds the N item rows grouped into

@@ -8,6 +8,10 @@ device; nothing is read from outside the tree.
     python scripts/bench_retrieval.py --M 10000 --N 100000000 --items bf16 --no-baseline --runs 1
     python scripts/bench_retrieval.py --no-baseline --filter    # + the filtered arms, --seen 256
 
+At --k > 256 (up to 8192) the ``fused`` arm is ops.topk_mips_large (tt_topk_mips_large: pooled radix
+selection); --large adds the arm ``fused_large``, that kernel at any k, with its ratio to ``fused`` and
+whether the two results are equal (at k <= 256 this prices the new selection where both exist).
+
 --filter adds two arms of tt_topk_mips_filtered to the interleaved runs: ``filtered_noop`` (an
 all-ones item mask and empty exclusion lists: the price of the filtered kernel itself) and
 ``filtered`` (a seeded mask with ~90 % ones and --seen seeded uniform item ids per query, sorted), and
@@ -93,6 +97,7 @@ def main():
     ap.add_argument("--splits", type=int, default=None)
     ap.add_argument("--no-baseline", action="store_true")
     ap.add_argument("--filter", action="store_true", help="add the filtered_noop and filtered arms")
+    ap.add_argument("--large", action="store_true", help="add the fused_large arm (tt_topk_mips_large at any k)")
     ap.add_argument("--seen", type=int, default=256, help="excluded ids per query of the filtered arm")
     ap.add_argument("--ivf", type=int, default=0, metavar="NLIST", help="add the IVF arms over an index of NLIST lists")
     ap.add_argument("--nprobe", default="1,8,32", help="comma-separated nprobe values of the IVF arms")
@@ -120,13 +125,18 @@ def main():
     q16 = q.to(torch.bfloat16)
     c16 = c if a.items == "bf16" or a.no_baseline else c.to(torch.bfloat16)  # the torch arm's operands (not timed)
 
-    def fused():
-        return ops.topk_mips(q, c, a.k, splits=a.splits)
+    def fused_large():
+        return ops.topk_mips_large(q, c, a.k, splits=a.splits)
+
+    def fused():  # past tt_topk_mips' limit of 256 the exact kernel is the pooled selection
+        return ops.topk_mips(q, c, a.k, splits=a.splits) if a.k <= 256 else fused_large()
 
     def composed():
         return torch_arm(q16, c16, a.k, a.chunk)
 
     arms = {"fused": fused} if a.no_baseline else {"fused": fused, "torch": composed}
+    if a.large:
+        arms["fused_large"] = fused_large
     if a.filter:
         ones = ops.pack_allow_mask(torch.ones(a.N, dtype=torch.bool, device=dev))
         empty = (torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(a.M + 1, dtype=torch.int64, device=dev))
@@ -209,6 +219,10 @@ def main():
             res[n]["ratio_to_fused"] = round(res[n]["median_ms"] / res["fused"]["median_ms"], 4)
         res["filtered_noop"]["equals_fused"] = bool(torch.equal(outs["filtered_noop"][0], outs["fused"][0]) and
                                                     torch.equal(outs["filtered_noop"][1], outs["fused"][1]))
+    if a.large:
+        res["fused_large"]["ratio_to_fused"] = round(res["fused_large"]["median_ms"] / res["fused"]["median_ms"], 4)
+        res["fused_large"]["equals_fused"] = bool(torch.equal(outs["fused_large"][0], outs["fused"][0]) and
+                                                  torch.equal(outs["fused_large"][1], outs["fused"][1]))
     if a.ivf:
         lens = index.list_len.to(torch.float64)
         res["ivf"] = {"nlist": a.ivf, "clusters": a.clusters, "sigma": a.sigma, "iters": a.ivf_iters,
@@ -241,9 +255,11 @@ def main():
         res["speedup_worst_case"] = round(res["torch"]["min_ms"] / res["fused"]["max_ms"], 2)
         # agreement of the two arms' id sets (the torch arm ranks bf16-rounded scores: not exact)
         fi, ti = outs["fused"][0], outs["torch"][0]
-        rows = slice(0, min(a.M, 256))
-        hit = (fi[rows].unsqueeze(2) == ti[rows].unsqueeze(1)).any(2).float().mean()
-        res["id_overlap_first_rows"] = round(float(hit), 4)
+        nrows = min(a.M, 256)
+        step = max(1, min(nrows, (1 << 28) // (a.k * a.k)))  # rows per comparison: k * k booleans each
+        hit = sum(float((fi[lo:min(lo + step, nrows)].unsqueeze(2) == ti[lo:min(lo + step, nrows)].unsqueeze(1))
+                        .any(2).float().sum()) for lo in range(0, nrows, step)) / (nrows * a.k)
+        res["id_overlap_first_rows"] = round(hit, 4)
     print(json.dumps(res), flush=True)
 
 

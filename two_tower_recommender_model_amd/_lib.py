@@ -45,6 +45,7 @@ TT_TOWER_GENERAL_T1 = 1
 TT_MAX_FEATURES = 64
 TT_MAX_TABLES = 64
 TT_TOPK_MAX_K = 256
+TT_TOPK_LARGE_MAX_K = 8192
 
 
 class TableMeta(C.Structure):
@@ -330,6 +331,9 @@ SIGNATURES = {
     "tt_topk_mips": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _sz, _vp]),
     "tt_topk_mips_filtered": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _sz, _vp]),
+    "tt_topk_mips_large_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
+    "tt_topk_mips_large": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _sz, _vp]),
     "tt_ivf_scan_workspace_bytes": (_sz, [_i64, _int, _int, _i64]),
     "tt_ivf_scan": (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp, _vp, _int,
                            _vp, _vp, _vp, _sz, _vp]),
@@ -401,6 +405,8 @@ COMPUTE_ENTRY_POINTS = [
 # later ABI 4 additions (csrc/ivf.hip): bound through SIGNATURES like the rest, not part of the
 # count above, which tt_num_entry_points() pins at the entry points up to tt_topk_mips_filtered
 IVF_ENTRY_POINTS = ["tt_ivf_scan", "tt_ivf_segment_mean", "tt_ivf_mask_lists", "tt_ivf_scan_masked"]
+# the same for the large-k selection (csrc/topk_large.hip)
+TOPK_LARGE_ENTRY_POINTS = ["tt_topk_mips_large_workspace_bytes", "tt_topk_mips_large"]
 
 _lib = None
 _lock = threading.Lock()

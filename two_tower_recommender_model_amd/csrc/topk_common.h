@@ -50,9 +50,9 @@ __device__ __forceinline__ void wave_sync() {
 // one wave's selection state in LDS
 struct WaveSel {
   u64* cbuf;    // [TK_QW][TK_CB]
-  u64* lscr;    // [TT_TOPK_MAX_K]
+  u64* lscr;    // [Sink::SCR] the sink's scratch: a list's copy [TT_TOPK_MAX_K], or a 256-bin histogram
   int* ccnt;    // [TK_QW] candidates buffered
-  int* lcnt;    // [TK_QW] entries of the partial list
+  int* lcnt;    // [TK_QW] entries of the partial list (of the pool)
   float* thrs;  // [TK_QW] score of the list's k-th entry (-inf while shorter; +inf: no such query)
 };
 

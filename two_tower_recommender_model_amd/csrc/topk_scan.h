@@ -32,12 +32,17 @@
 // too, so an excluded key never raises a threshold, never enters a list and never displaces an
 // eligible item; all it costs is its place in the buffer until the next merge.
 //
-// A source (ExactSrc in retrieval.hip, IvfSrc in ivf.hip) describes a workgroup's work unit:
+// Where a full buffer goes is the scan's sink (ListSink below: the sorted partial list just described;
+// PoolSink in topk_large.hip: an unsorted pool pruned by radix selection, for k up to 8192). The scan,
+// the candidate path, the mask and the exclusion drop are the same for both.
+//
+// A source (ExactSrc in topk_exact.h, IvfSrc in ivf.hip) describes a workgroup's work unit:
 //   a                     the kernel's arguments: q, ldq, q_bf16, bias, k, excl_offsets
 //   n_beg, n_end, nchunks the item range [n_beg, n_end) and its chunks
 //   computes()            false: the wave has no queries and only helps to stage
 //   query(q)              the query of wave-local query q, -1: none
 //   has_list(q), lists    q has a partial list (the wave's first so many have), at lists + q * k
+//                         (the sink's layout: PoolSink's pools are 2 k + 32 keys apart)
 //   wave_excl             EXCL: some query of the wave has a non-empty exclusion segment
 //   excl_values, excl(q)  EXCL: the exclusion lists' values; q's two offsets into them
 //   index(n)              the item index that row n's key carries
@@ -62,14 +67,32 @@ struct ScanShape {
   static constexpr int MW = IC / 32;                 // mask words per chunk
 };
 
-template <int KS, bool BIAS, bool EXCL, bool MASK, class Src>
+// The sink of the scan: what happens to a query's full candidate buffer (absorb: the buffer is empty
+// afterwards and thrs[q] holds the new threshold) and what the final flush leaves in the workspace.
+// `lists` is the wave's first query's storage. SCR: the 8-byte words of per-wave LDS scratch it
+// needs (WaveSel::lscr). ListSink keeps a sorted list of k keys per query (k <= TT_TOPK_MAX_K);
+// topk_large.hip has the sink for larger k
+struct ListSink {
+  static constexpr int SCR = TT_TOPK_MAX_K;
+  static __device__ __forceinline__ void absorb(const WaveSel w, int q, u64* lists, int k, int lane) {
+    topk_merge_query(w, q, lists + (int64_t)q * k, k, lane);
+  }
+  // merge what is buffered; pad a list shorter than k
+  static __device__ __forceinline__ void flush(const WaveSel w, int q, u64* lists, int k, int lane) {
+    u64* gl = lists + (int64_t)q * k;
+    if (w.ccnt[q] > 0) topk_merge_query(w, q, gl, k, lane);
+    for (int i = w.lcnt[q] + lane; i < k; i += 64) gl[i] = 0ull;
+  }
+};
+
+template <int KS, bool BIAS, bool EXCL, bool MASK, class Sink = ListSink, class Src>
 __device__ __forceinline__ void topk_scan_body(Src& s) {
   constexpr int STRIDE = ScanShape<KS>::STRIDE, TK_IC = ScanShape<KS>::IC;
   __shared__ __attribute__((aligned(16))) __bf16 items[2][TK_IC * STRIDE];
   __shared__ __attribute__((aligned(16))) float bias_s[2][TK_IC];
   __shared__ uint32_t mask_s[2][ScanShape<KS>::MW];  // MASK only (no LDS without it)
   __shared__ u64 cbuf_s[TK_WAVES][TK_QW * TK_CB];
-  __shared__ u64 lscr_s[TK_WAVES][TT_TOPK_MAX_K];
+  __shared__ u64 lscr_s[TK_WAVES][Sink::SCR];
   __shared__ int ccnt_s[TK_WAVES][TK_QW];
   __shared__ int lcnt_s[TK_WAVES][TK_QW];
   __shared__ float thrs_s[TK_WAVES][TK_QW];
@@ -197,7 +220,7 @@ __device__ __forceinline__ void topk_scan_body(Src& s) {
                     continue;  // nothing left to merge, and the buffer is empty
                 }
               }
-              topk_merge_query(w, qi, s.lists + (int64_t)qi * k, k, lane);
+              Sink::absorb(w, qi, s.lists, k, lane);
             }
             if (merged) base = w.ccnt[q];
             int slot = base + ex;
@@ -215,18 +238,16 @@ __device__ __forceinline__ void topk_scan_body(Src& s) {
     __syncthreads();
   }
 
-  // flush the buffers; pad the lists shorter than k
+  // flush the buffers
 #pragma unroll 1
   for (int q = 0; q < TK_QW; ++q) {
     if (!s.has_list(q)) break;
-    u64* gl = s.lists + (int64_t)q * k;
     if constexpr (EXCL) {
       if (w.ccnt[q] > 0 && s.wave_excl) {
         if (s.query(q) >= 0) topk_drop_excluded(w, q, s.excl_values, s.excl(q), lane);
       }
     }
-    if (w.ccnt[q] > 0) topk_merge_query(w, q, gl, k, lane);
-    for (int i = w.lcnt[q] + lane; i < k; i += 64) gl[i] = 0ull;
+    Sink::flush(w, q, s.lists, k, lane);
   }
 }
 

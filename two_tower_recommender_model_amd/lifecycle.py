@@ -25,7 +25,7 @@ from typing import TYPE_CHECKING, Dict, Iterable, List, Optional, Sequence, Tupl
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .metrics import AUROC
 
 if TYPE_CHECKING:
@@ -195,13 +195,42 @@ def _retrieval_filters(N: int, M: int, device, allow, seen_values, seen_offsets)
     return allow, (rows, offsets)
 
 
+# The workspace one call of the large-k selection (256 < k <= 8192) may take: it holds splits * M pools
+# of 2 k + 32 keys, and retrieve()'s default of 65,536 queries per call would be 8.6 GB at k = 8192 with
+# one split alone. 4 GiB is 1.4 % of an MI355X's HBM and about the size of the reference-scale item
+# embeddings beside it; it still gives every CU a workgroup at k = 8192 (32,700 pools = 255
+# workgroups of 128 queries) and near-full residency at the reference's k = 5000 (53,500 pools).
+LARGE_K_WORKSPACE_BYTES = 4 << 30
+
+
+def _check_index_k(k: int, index) -> None:
+    if index is not None and k > _lib.TT_TOPK_MAX_K:
+        raise ValueError(f"k = {k} with an index: the IVF list scan's limit is k <= {_lib.TT_TOPK_MAX_K} "
+                         "(exact retrieval, index=None, goes up to 8192)")
+
+
+def _large_k_plan(M: int, N: int, k: int, query_chunk: int) -> Tuple[int, Optional[int]]:
+    """(queries per call, splits) of the large-k selection under LARGE_K_WORKSPACE_BYTES: the chunk is
+    ``query_chunk`` lowered to the pools that fit (whole workgroups of 128 queries where it is cut);
+    splits is None (the library's choice) where that fits too, else what is left of the pools."""
+    pools = max(1, LARGE_K_WORKSPACE_BYTES // ((2 * k + 32) * 8))
+    n = min(query_chunk, M)
+    if n > pools:
+        n = max(pools // 128 * 128, min(pools, 128))
+    auto = ops.topk_mips_large_workspace_bytes(n, N, k)
+    if 0 < auto <= LARGE_K_WORKSPACE_BYTES:
+        return n, None
+    return n, max(1, min(64, pools // n))
+
+
 def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metric: str = "dot",
              query_chunk: int = 1 << 16, bias: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
              seen_values: Optional[torch.Tensor] = None, seen_offsets: Optional[torch.Tensor] = None,
              index: Optional["IVFIndex"] = None, nprobe: int = 32) -> Tuple[torch.Tensor, torch.Tensor]:
     """The query loop of 04_evaluate_retrieval.py:131-153 without an index: for each row of
-    ``user_emb`` the exact top ``k`` rows of ``item_emb`` (ops.topk_mips), ``query_chunk`` queries per
-    launch. ``metric``: "dot" (the model's own score) or "l2" (the order of the reference's vector
+    ``user_emb`` the exact top ``k`` rows of ``item_emb`` (ops.topk_mips; ops.topk_mips_large for
+    256 < k <= 8192, with ``query_chunk`` lowered so that a call's workspace stays under
+    LARGE_K_WORKSPACE_BYTES), ``query_chunk`` queries per launch. ``metric``: "dot" (the model's own score) or "l2" (the order of the reference's vector
     index; ``bias`` = l2_bias(item_emb), computed here when not passed). Returns (ids [M, k] int64
     in the reference's labels — row i is id i + 1, as export_embeddings; 0 past the table —, scores
     [M, k] fp32: q.c, or q.c - 0.5 |c|^2 for "l2").
@@ -219,9 +248,10 @@ def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metri
     read (the index holds its own copy). An item mask goes to the index itself, as the reference's
     ``filters=`` does: pass ``index=index.restricted(allow)`` (the coarse step then counts only lists
     with an eligible item, the fine step is the masked list scan); ``allow=`` beside ``index=`` is
-    refused."""
+    refused, and so is k > 256 (the IVF list scan's limit)."""
     if metric not in ("dot", "l2"):
         raise ValueError("metric must be 'dot' or 'l2'")
+    _check_index_k(k, index)
     if index is not None:
         if allow is not None:
             raise ValueError("allow masks are not supported with an index: pass index=index.restricted(allow) "
@@ -239,10 +269,18 @@ def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metri
     allow, seen = _retrieval_filters(item_emb.shape[0], M, user_emb.device, allow, seen_values, seen_offsets)
     ids = torch.empty(M, k, dtype=torch.int64, device=user_emb.device)
     scores = torch.empty(M, k, dtype=torch.float32, device=user_emb.device)
+    large = k > _lib.TT_TOPK_MAX_K  # the pooled selection (ops.topk_mips_large), its workspace bounded
+    splits = None
+    if large and k <= _lib.TT_TOPK_LARGE_MAX_K and M > 0:
+        query_chunk, splits = _large_k_plan(M, item_emb.shape[0], k, query_chunk)
     for lo in range(0, M, query_chunk):
         n = min(query_chunk, M - lo)
         exclude = None if seen is None else (seen[0], seen[1][lo:lo + n + 1])
-        i, s = ops.topk_mips(user_emb[lo:lo + n], item_emb, k, bias=bias, allow=allow, exclude=exclude)
+        if large:
+            i, s = ops.topk_mips_large(user_emb[lo:lo + n], item_emb, k, bias=bias, splits=splits, allow=allow,
+                                       exclude=exclude)
+        else:
+            i, s = ops.topk_mips(user_emb[lo:lo + n], item_emb, k, bias=bias, allow=allow, exclude=exclude)
         ids[lo:lo + query_chunk] = i + 1
         scores[lo:lo + query_chunk] = s
     return ids, scores
@@ -258,6 +296,7 @@ def retrieve_fused(step, user_rows: torch.Tensor, k: int = 100, metric: str = "d
     (export_fused, unless its embeddings ``item_emb`` are passed in). ``allow``, ``seen_values`` /
     ``seen_offsets``, ``query_chunk``, ``index`` and ``nprobe`` as retrieve() (with an index the
     item tower is not run; an item mask with an index is ``index=index.restricted(allow)``)."""
+    _check_index_k(k, index)
     towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
     x = step.tables.table_view(0)[user_rows.to(step.device)]
     for w, b in towers[0]:

@@ -908,6 +908,38 @@ def sort_exclusions(values: torch.Tensor, offsets: torch.Tensor, N: int) -> torc
     return (codes - owner * (N + 1)).to(torch.int32)
 
 
+def _topk_operands(what: str, queries, items, k, bias, splits, allow, exclude):
+    """The argument checks and the outputs shared by topk_mips and topk_mips_large: (M, N, E, device,
+    splits as the ABI takes them, ids, scores, exclusion values, exclusion offsets)."""
+    _dev(queries, items, bias, allow)
+    if exclude is not None:
+        _dev(*exclude)
+    if queries.dim() != 2 or items.dim() != 2 or queries.shape[1] != items.shape[1] or \
+            queries.stride(1) != 1 or items.stride(1) != 1:
+        raise _lib.TTError(f"{what}: queries [M, E] and items [N, E], last dimension contiguous")
+    M, E = queries.shape
+    N = items.shape[0]
+    dev = queries.device
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous()):
+        raise _lib.TTError(f"{what}: bias must be contiguous fp32 [N]")
+    S = 0 if splits is None else int(splits)
+    ids = torch.empty(M, k, dtype=torch.int64, device=dev)
+    scores = torch.empty(M, k, dtype=torch.float32, device=dev)
+    if allow is not None and (allow.dtype != torch.int32 or allow.dim() != 1 or allow.numel() != (N + 31) // 32 or
+                              not allow.is_contiguous()):
+        raise _lib.TTError(f"{what}: allow must be contiguous int32 [ceil(N / 32)] (pack_allow_mask)")
+    xv = xo = None
+    if exclude is not None:
+        xv, xo = exclude
+        if xv.dtype != torch.int32 or xv.dim() != 1 or not xv.is_contiguous():
+            raise _lib.TTError(f"{what}: exclude values must be contiguous int32 [L]")
+        if xo.dtype != torch.int64 or xo.dim() != 1 or xo.numel() != M + 1 or not xo.is_contiguous():
+            raise _lib.TTError(f"{what}: exclude offsets must be contiguous int64 [M + 1]")
+        if xv.numel() == 0:  # no values: every segment is empty
+            xv = xo = None
+    return M, N, E, dev, S, ids, scores, xv, xo
+
+
 def topk_mips(queries: torch.Tensor, items: torch.Tensor, k: int, bias: Optional[torch.Tensor] = None,
               splits: Optional[int] = None, allow: Optional[torch.Tensor] = None,
               exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -924,33 +956,8 @@ def topk_mips(queries: torch.Tensor, items: torch.Tensor, k: int, bias: Optional
     the offsets are absolute and must lie within ``values``) restrict each query to its eligible
     items (tt_topk_mips_filtered): the same lists as over those items alone, -1 / -inf where fewer
     than k are eligible. With both None this is the unfiltered call."""
-    _dev(queries, items, bias, allow)
-    if exclude is not None:
-        _dev(*exclude)
-    if queries.dim() != 2 or items.dim() != 2 or queries.shape[1] != items.shape[1] or \
-            queries.stride(1) != 1 or items.stride(1) != 1:
-        raise _lib.TTError("topk_mips: queries [M, E] and items [N, E], last dimension contiguous")
-    M, E = queries.shape
-    N = items.shape[0]
-    dev = queries.device
-    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != N or not bias.is_contiguous()):
-        raise _lib.TTError("topk_mips: bias must be contiguous fp32 [N]")
-    S = 0 if splits is None else int(splits)
+    M, N, E, dev, S, ids, scores, xv, xo = _topk_operands("topk_mips", queries, items, k, bias, splits, allow, exclude)
     lib = _lib_()
-    ids = torch.empty(M, k, dtype=torch.int64, device=dev)
-    scores = torch.empty(M, k, dtype=torch.float32, device=dev)
-    if allow is not None and (allow.dtype != torch.int32 or allow.dim() != 1 or allow.numel() != (N + 31) // 32 or
-                              not allow.is_contiguous()):
-        raise _lib.TTError("topk_mips: allow must be contiguous int32 [ceil(N / 32)] (pack_allow_mask)")
-    xv = xo = None
-    if exclude is not None:
-        xv, xo = exclude
-        if xv.dtype != torch.int32 or xv.dim() != 1 or not xv.is_contiguous():
-            raise _lib.TTError("topk_mips: exclude values must be contiguous int32 [L]")
-        if xo.dtype != torch.int64 or xo.dim() != 1 or xo.numel() != M + 1 or not xo.is_contiguous():
-            raise _lib.TTError("topk_mips: exclude offsets must be contiguous int64 [M + 1]")
-        if xv.numel() == 0:  # no values: every segment is empty
-            xv = xo = None
     ws = scratch(lib.tt_topk_mips_workspace_bytes(M, N, k, S), dev, "topk_mips")
     if allow is None and xv is None:
         check(lib.tt_topk_mips(ptr(queries), _x_code(queries), queries.stride(0), ptr(items), _x_code(items),
@@ -962,6 +969,29 @@ def topk_mips(queries: torch.Tensor, items: torch.Tensor, k: int, bias: Optional
                                         ptr(ids), ptr(scores), ptr(ws), ws.numel(), stream_handle(dev)),
               "topk_mips_filtered")
     return ids, scores
+
+
+def topk_mips_large(queries: torch.Tensor, items: torch.Tensor, k: int, bias: Optional[torch.Tensor] = None,
+                    splits: Optional[int] = None, allow: Optional[torch.Tensor] = None,
+                    exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """topk_mips for ``k`` up to 8192 (tt_topk_mips_large: an unsorted pool per query, pruned by a radix
+    select of its k-th key, instead of a sorted list): candidate generation for a ranker. Arguments,
+    checks and return values are topk_mips'; the result is the same unique one — bit-identical across
+    runs and ``splits``, to topk_mips for k <= 256, and in its first 256 columns to topk_mips(k = 256)
+    for any k. The workspace is splits * M * (2 k + 32) * 8 bytes."""
+    M, N, E, dev, S, ids, scores, xv, xo = _topk_operands("topk_mips_large", queries, items, k, bias, splits, allow,
+                                                          exclude)
+    lib = _lib_()
+    ws = scratch(lib.tt_topk_mips_large_workspace_bytes(M, N, k, S), dev, "topk_mips_large")
+    check(lib.tt_topk_mips_large(ptr(queries), _x_code(queries), queries.stride(0), ptr(items), _x_code(items),
+                                 items.stride(0), ptr(bias), M, N, E, k, S, ptr(allow), ptr(xv), ptr(xo), ptr(ids),
+                                 ptr(scores), ptr(ws), ws.numel(), stream_handle(dev)), "topk_mips_large")
+    return ids, scores
+
+
+def topk_mips_large_workspace_bytes(M: int, N: int, k: int, splits: Optional[int] = None) -> int:
+    """tt_topk_mips_large_workspace_bytes: what one topk_mips_large call takes (0 outside the limits)."""
+    return int(_lib_().tt_topk_mips_large_workspace_bytes(M, N, k, 0 if splits is None else int(splits)))
 
 
 def ivf_scan(queries: torch.Tensor, rows: torch.Tensor, labels: torch.Tensor, list_begin: torch.Tensor,
