@@ -6,7 +6,7 @@ The embedding update groups a step's lookups by unique (table, row) in open-addr
 linear probing, one compare-and-swap per probe, wrapping at cap - 1:
 
   1. the dedup global table        dd_insert* (csrc/dedup.h), cap = dedup_cap(max_lookups) 128-B slots
-  2. the ring insert role's LDS    insert_next_full_block (csrc/tower.hip), INS_HS slots per workgroup
+  2. the ring insert role's LDS    insert_next_full_block (csrc/tower_tail.hip), INS_HS slots per workgroup
   3. the KJT-form global table     hash_insert / bwd_tile_hash_kernel (csrc/embedding.hip), bwd_cap()
   4. the KJT-form chunk LDS table  bwd_tile_hash_kernel, TILE_HS slots per chunk of <= TILE_CH lookups
   5. the deferred-insert resolver  dd_insert_defer_finish_at / dd_resolve_block: table 1 again
@@ -39,8 +39,8 @@ HOT_SPLIT = 512       # csrc/embedding.hip line 214: a hot row above it is split
 TILE_BAGS = 16        # csrc/embedding.hip line 222: bags per workgroup of bwd_tile_hash_kernel
 TILE_CH = 1024        # csrc/embedding.hip line 223: lookups per chunk
 TILE_HS = 2048        # csrc/embedding.hip line 224: LDS hash slots per chunk
-INS_HS = 1024         # csrc/tower.hip line 2667: LDS hash slots of one ring insert workgroup
-INS_GROUP = 256       # csrc/tower.hip insert_next_full_block: INS_PT = 1 lookup per thread, 256 threads
+INS_HS = 1024         # csrc/tower_tail.hip line 992: LDS hash slots of one ring insert workgroup
+INS_GROUP = 256       # csrc/tower_tail.hip insert_next_full_block: INS_PT = 1 lookup per thread, 256 threads
 DEDUP_CAP_MIN, DEDUP_CAP_FACTOR = 1024, 16  # csrc/dedup.hip dedup_cap (line 34): c = 1024; while (c < 16 * L)
 BWD_CAP_MIN, BWD_CAP_FACTOR = 4096, 2       # csrc/embedding.hip bwd_cap (line 264): c = SCAN_TILE; while (c < 2 * L)
 MAX_FAMILY = 96       # keys asked of one home slot: every slot has more candidates among 2^21 rows

@@ -238,7 +238,7 @@ def test_mixer_pinned_to_source(fname, func):
 
 
 def test_constants_pinned_to_source():
-    dh, dc, eh, th = _src("dedup.h"), _src("dedup.hip"), _src("embedding.hip"), _src("tower.hip")
+    dh, dc, eh, th = _src("dedup.h"), _src("dedup.hip"), _src("embedding.hip"), _src("tower_tail.hip")
     for text, names in ((dh, ("DD_TABLE_SHIFT", "DD_CNT_BITS", "DD_INL")),
                         (eh, ("PK_ROW_BITS", "PK_CNT_BITS", "HOT_MIN", "HOT_SPLIT", "TILE_BAGS", "TILE_CH", "TILE_HS")),
                         (th, ("INS_HS",))):

@@ -1,6 +1,6 @@
 """T3's segment select and slab reduction against torch in the kernel's own order (``-m gpu``).
 
-update_block (csrc/tower.hip) finds a parameter's segment (W or b of tower t, layer l) by compares
+update_block (csrc/tower_tail.hip) finds a parameter's segment (W or b of tower t, layer l) by compares
 and selects over a table of records held in SGPRs, and issues its slab loads before it knows the
 segment: a W element sums the S slabs in the order s = 0, 1, ..., a bias element keeps slab 0's
 value. Here the slabs in the workspace are overwritten with random numbers (so a wrong segment, a

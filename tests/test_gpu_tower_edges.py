@@ -11,8 +11,12 @@ elsewhere pass int32 0 / 1 labels and grad_scale = 1 only. The families, by entr
   kjt             fwd_bwd_kjt, D = 128, B = 200                  the two-layer kernel, sum pool inside
   indexed-f32     fwd_bwd_indexed, fp32 rows, D = 128, B = 136   the two-layer kernel, rows by position
   indexed-bf16    fwd_bwd_indexed, bf16 rows, D = 128, B = 136   the row-owned kernel, rows by position
+  indexed-f32-64  fwd_bwd_indexed, fp32 rows, D = 64, B = 136    the two-layer kernel's D = 64 form
+  indexed-bf16-l2 fwd_bwd_indexed, bf16 rows, [96, 32] -> [96, 32], B = 136   the two-layer kernel, bf16
+                                                                 rows at a run-time shape
 
-Each run is T1 -> wgrad(loss) -> update(do_adam = False, grads_out = ...). The int32 run of every
+With these every tower_l2_kernel instantiation of the library is launched by the suite (the multi-hot
+D = 64 one by tests/test_gpu_abi_edges.py). Each run is T1 -> wgrad(loss) -> update(do_adam = False, grads_out = ...). The int32 run of every
 family is anchored to the fp64 emulation of the kernels' rounding points (tests/tower_emul.py
 emulate_bounds / check_towers; loss rtol 1e-4 as tests/test_gpu_baseline_parity.py); label dtypes
 and the power-of-two grad_scale are then compared with that run bit for bit."""
@@ -36,6 +40,8 @@ FAMILIES = {
     "kjt": ("kjt", 200, [128, 128], [128, 64]),
     "indexed-f32": ("indexed", 136, [128, 128], [128, 64]),
     "indexed-bf16": ("indexed-bf16", 136, [128, 128], [128, 64]),
+    "indexed-f32-64": ("indexed", 136, [64, 64], [128, 64]),
+    "indexed-bf16-l2": ("indexed-bf16", 136, [96, 32], [96, 32]),
 }
 
 
@@ -147,7 +153,9 @@ class Family:
             tw.update(self.P, do_adam=False, grads_out=grads)
             torch.cuda.synchronize()
             out["grad_rows"] = [x.cpu() for x in gro]
-            out["dx"] = [x[p.clamp(min=0).to(torch.int64)] for x, p in zip(out["grad_rows"], self.pos)]
+            # a dropped id has no gradient row: zeros (row 0 may be a row no position names: the sentinel)
+            out["dx"] = [torch.where((p >= 0)[:, None], x[p.clamp(min=0).to(torch.int64)], torch.zeros(()))
+                         for x, p in zip(out["grad_rows"], self.pos)]
         out.update(logits=logits.cpu(), loss=loss.cpu(), grads=grads.cpu())
         return out
 

@@ -1,7 +1,7 @@
 """The fused tower kernels swept over their declared shape limits (``-m gpu``).
 
 tests/tower_shapes.py holds the cases: each is the smallest shape at which one run-time branch of
-csrc/tower.hip exists (L = 1 and L = 4, the 16-tile boundary of the staged T2, wave predication at
+csrc/tower*.hip exists (L = 1 and L = 4, the 16-tile boundary of the staged T2, wave predication at
 widths 32 / 96 and rising widths, a partial 128-column input chunk, a 32-wide tower on the register
 T2, ragged T2 slices, the run-time two-layer kernel away from [96, 32], B = 8, and the indexed
 multi-feature T1 at D = 16 / 32 / 128). Every case runs T1 -> wgrad(loss) -> update(do_adam = False,

@@ -2,7 +2,7 @@
 
 tt_tower_shape_t admits 1..4 layers, widths that are multiples of 32 in [32, 128], tower inputs that
 are multiples of 32 in [32, 1024] and any B % 8 == 0. Each case below is the smallest shape at which
-one run-time branch of csrc/tower.hip exists (the `branch` column). The table is shared by
+one run-time branch of csrc/tower*.hip exists (the `branch` column). The table is shared by
 tests/test_gpu_tower_shapes.py (the kernels against the fp64 emulation of tests/tower_emul.py) and
 tests/test_cpu_tower_shapes.py (the emulation and its thresholds checked without a GPU).
 
@@ -32,7 +32,7 @@ SENT = -77.125     # finite sentinel of every output buffer
 FROB_RTOL = 2e-3   # relative Frobenius error of a whole dX / gradient tensor (test_gpu_ops' number)
 GENERAL_T1 = 1     # TT_TOWER_GENERAL_T1
 
-# csrc/tower.hip constants the layout depends on
+# csrc/tower_common.h constants the layout depends on
 TR, MAXW, MAXL, XCH = 32, 128, 4, 128
 T2_NT, T2_PASS = 64, 256
 
@@ -47,7 +47,7 @@ def _align(n: int, a: int = 256) -> int:
 
 @dataclass(frozen=True)
 class Layout:
-    t1: str          # "rows" | "l2-fixed" | "l2-runtime" | "general"
+    t1: str          # "rows" | "l2-runtime" | "general"
     t2: str          # "staged" | "register"
     S: int           # T2 slices = slab depth T3 reduces over
     mslice: int      # rows per slice

@@ -1,5 +1,5 @@
 // Device code of the sharded route (requester side of input_dist), shared by csrc/shard.hip (its
-// own launches) and csrc/tower.hip (the route of the next batch as extra workgroups of the towers'
+// own launches) and csrc/tower_tail.hip (the route of the next batch as extra workgroups of the towers'
 // T2 / T3 launches in the pipelined sharded step). See shard.hip for the exchange's layout.
 #pragma once
 
@@ -132,7 +132,7 @@ __device__ __forceinline__ void route_place_block(const RouteArgs& a, int blk, i
 }
 
 // Owner side of the pipelined exchange (tt_shard_gather_segs_bf16, and the pipelined step's
-// combined launch in csrc/tower.hip): the keys of source s sit in source block s of the received
+// combined launch in csrc/tower_tail.hip): the keys of source s sit in source block s of the received
 // buffer (int64 view: block s at s * blk64, counts at + cnt64, the slots of feature f at + cnt64 + F
 // + seg_off[f]); slot j of source s (j < S) -> rows_out[s * out_stride + j] (bf16) and, with the
 // dedup on, lookup s * S + j. A half-wave per slot.
@@ -258,13 +258,13 @@ __device__ __forceinline__ void shard_gather_block(const GatherSegArgs& a, int b
 }
 
 // host: the route's arguments from its role (tt_shard_route_cols / _segs and the fused launches of
-// csrc/tower.hip). seg_capacity: the uniform layout of tt_shard_route_cols (r.segs and r.pos_out
+// csrc/tower_tail.hip). seg_capacity: the uniform layout of tt_shard_route_cols (r.segs and r.pos_out
 // unused), or RT_SEGS: the segment table r.segs. B = 0 passes (the exports then launch nothing).
 constexpr int64_t RT_SEGS = -1;
 int route_args(const tt_route_role_t& r, int64_t B, int64_t seg_capacity, const char* what, RouteArgs& a);
 
 // host: the owner-side gather's arguments from its role (tt_shard_gather_segs_bf16 and launch G of
-// csrc/tower.hip, whose role may carry direct stores); F and W are the route's
+// csrc/tower_tail.hip, whose role may carry direct stores); F and W are the route's
 int gather_segs_args(const tt_gather_role_t& ga, int F, int W, GatherSegArgs& a);
 
 }  // namespace tt

@@ -182,11 +182,6 @@ class FusedTwoTowerStep:
         if self.dedup_single:
             self.tables.ensure_dedup_workspace(F * B)
         self.materialize_pooled = bool(materialize_pooled)
-        # ring: tower_l2_kernel's dedup wave touches the next batch's rows after its own gather (cache
-        # / TLB prefetch); the row-owned T1 touches nothing (there the touches' TLB misses stall the
-        # workgroup's later stores, and beside T3 they cost T3 more than they save T1: DESIGN.md
-        # section 3)
-        self.prefetch_next = True
         # ring: T2 + complete next-batch insert + update of the rows looked up more than once in one
         # launch, then T3 alone (False, tests: T2 + deferred insert, then resolver + update + T3)
         self.ring_tail = True
@@ -647,8 +642,7 @@ class FusedTwoTowerStep:
             ptr_array([ts.table_view(0), ts.table_view(1)]), ptr_array([ts.state_view(0), ts.state_view(1)]),
             ptr(self.pooled) if self.materialize_pooled else None, self.gpooled.stride(0), ptr(self.gpooled),
             ptr(self.params), ptr(labels), _lib.TT_I32, 1.0, ptr(self.logits), self.lr_emb, self.eps, ptr(ws),
-            ws.numel(), ts._dd_cap, ptr_array(list(next_cols)) if self.prefetch_next else None, ptr(tw.ws),
-            tw.nbytes, st), "tower_fwd_bwd_gather_update")
+            ws.numel(), ts._dd_cap, None, ptr(tw.ws), tw.nbytes, st), "tower_fwd_bwd_gather_update")
         self._mark("t1", 1)
         if self.ring_tail:
             self._mark("tail", 0)
