@@ -45,6 +45,8 @@
  *   tt_topk_mips_filtered      <- the same query with the index's `filters=` (04:100, an item mask
  *                                 shared by all queries) and each user's seen items excluded
  *   tt_topk_mips_large         <- the same query at k in the thousands (04:91 asks for k = 5000)
+ *   tt_target_ranks            <- the evaluation of those queries (04:202-226) from each held-out
+ *                                 item's exact rank in the whole catalogue: every k at once, no top-k
  *   tt_launch (a launch plan)  <- the same backward work with several roles in one launch: the
  *                                 weight gradients beside the embedding update / next-batch insert /
  *                                 shard route and gather ("launch plans" below)
@@ -682,6 +684,56 @@ int tt_topk_mips_large(const void* queries, int q_dtype, int64_t ldq, const void
                        const float* bias, int64_t M, int64_t N, int E, int k, int splits, const uint32_t* allow,
                        const int32_t* excl_values, const int64_t* excl_offsets, int64_t* ids, float* scores,
                        void* workspace, size_t ws_bytes, void* stream);
+
+/* Full-catalogue target ranks (ABI 4 addition; not part of tt_num_entry_points()): what a retrieval
+ * evaluation needs of a query's order of the whole catalogue — the rank of each held-out item — without
+ * any top-k list. From the ranks follow recall@k and nDCG@k for every k at once, MRR and the mean rank
+ * (the full-ranking protocol). No k, no selection, no candidate buffers or k-sized workspace: the work
+ * is tt_topk_mips' score stream plus a few compares per score.
+ * Operands, dtypes, strides, rounding, `bias`, `allow`, `excl_values` / `excl_offsets` and `splits` are
+ * tt_topk_mips_filtered's. Query m's targets are the item row indices
+ * target_values[target_offsets[m] .. target_offsets[m + 1]): target_offsets has M + 1 absolute
+ * entries into target_values (length T_cap); they need not start at 0, so a chunk of the queries is
+ * served by a view of the offsets. ranks (int64) and scores (fp32, may be NULL) are indexed like
+ * target_values; only positions in [target_offsets[0], target_offsets[M]) are written. L_cap is the
+ * length of excl_values (0 when both exclusion pointers are NULL). There is no limit on the targets
+ * of a query.
+ * CONTRACT, for query m and its target t:
+ *   rank: the number of items n eligible for m that precede t in the total order "higher score
+ *     first, equal scores by lower index" (make_key(s(m, n), n) > make_key(s(m, t), t)); 0-based, the
+ *     best item has rank 0.
+ *   score: s is tt_topk_mips' score: fp32 operands rounded to bf16 (nearest-even) on load, the bf16
+ *     MFMA chain over E in ascending k-steps from a zero accumulator, then + bias[n]; a function of
+ *     the two rows and the bias only.
+ *   eligibility: tt_topk_mips_filtered's: the allow bit is set (NULL: every item) and n is not in
+ *     m's exclusion segment.
+ *   an ineligible target — its index outside [0, N), denied by `allow`, or in m's own exclusion
+ *     segment — gets rank -1 and score -inf.
+ *   equivalence: for every eligible target, rank(m, t) == j exactly when column j of
+ *     tt_topk_mips_filtered's list of query m holds t, for any k > j, and scores holds that column's
+ *     score bits.
+ *   reproducibility: bit-identical across runs, split counts and query chunkings.
+ * Execution: four launches on `stream` (the slabs of at most 8 targets that each query's targets are
+ * cut into; the scores of the (query, target) pairs and of the exclusion items; the scan over (slab
+ * tiles x item splits) with per-split counts; the sum and the exclusion correction per target); no
+ * allocation, no synchronisation, nothing read back: the slab count stays on the device and the
+ * grids are sized to its bound. Device data cannot cause an out-of-range access: target or exclusion
+ * offsets that decrease, are negative or point past T_cap / L_cap make that query's segment empty;
+ * values are range-checked before they index anything. Where segments of different queries overlap
+ * (more values in all than T_cap), the queries past the bound are not served.
+ * Workspace: tt_target_ranks_workspace_bytes — about 4 (S + 1) T_cap + 4 L_cap + 16 (T_cap / 8 +
+ * L_cap / 16 + 2 M) bytes with S the split count; it need not be initialised.
+ * Limits (TT_EINVAL otherwise, before any launch): E a multiple of 32 in [32, 128]; 1 <= M <= 2^30;
+ * 1 <= N < 2^31; 0 <= T_cap, L_cap < 2^31; splits 0 or in [1, 64]; dtypes TT_F32 / TT_BF16; ldq,
+ * ldc >= E; excl_values and excl_offsets both NULL (then L_cap = 0) or both given; queries, items,
+ * target_offsets, ranks, workspace (and target_values when T_cap > 0) not NULL; ws_bytes >= the
+ * workspace query, which returns 0 for arguments outside the limits. Scores must be finite. */
+size_t tt_target_ranks_workspace_bytes(int64_t M, int64_t N, int64_t T_cap, int64_t L_cap, int splits);
+int tt_target_ranks(const void* queries, int q_dtype, int64_t ldq, const void* items, int c_dtype, int64_t ldc,
+                    const float* bias, int64_t M, int64_t N, int E, const int32_t* target_values,
+                    const int64_t* target_offsets, int64_t T_cap, const uint32_t* allow, const int32_t* excl_values,
+                    const int64_t* excl_offsets, int64_t L_cap, int splits, int64_t* ranks, float* scores /* nullable */,
+                    void* workspace, size_t ws_bytes, void* stream);
 
 /* IVF (inverted-file) approximate top-k (ABI 4 addition): the fine step of the approximate vector
  * index that 04_evaluate_retrieval.py:112-153 queries. The index holds the N item rows grouped into

@@ -38,6 +38,13 @@ eligible item); and the same pair at a "department" mask, the items of every 20t
 (``ivf_npP_maskeddept_plain`` / ``_aware``): a uniform mask leaves an eligible item in every list, a
 structured one empties most of a query's nearest lists. Each arm's recall@k is against the exact ops.topk_mips(allow=) ids of its mask; the
 time of restricted() itself is printed per mask.
+
+    python scripts/bench_retrieval.py --no-baseline --ranks 1,8,20
+
+--ranks T (or a comma-separated list) adds, per value, the arm ``ranks_tT`` to the interleaved runs:
+ops.target_ranks (tt_target_ranks: each target's exact rank in the whole catalogue, no top-k) of T seeded
+uniform random targets per query, with its ratio to ``fused`` of the same process, the number of
+(query, target) pairs and the mean rank it found (uniform targets: about N / 2).
 """
 import argparse
 import json
@@ -99,6 +106,7 @@ def main():
     ap.add_argument("--filter", action="store_true", help="add the filtered_noop and filtered arms")
     ap.add_argument("--large", action="store_true", help="add the fused_large arm (tt_topk_mips_large at any k)")
     ap.add_argument("--seen", type=int, default=256, help="excluded ids per query of the filtered arm")
+    ap.add_argument("--ranks", default="", metavar="T", help="add the ranks_tT arms: T random targets per query (comma-separated)")
     ap.add_argument("--ivf", type=int, default=0, metavar="NLIST", help="add the IVF arms over an index of NLIST lists")
     ap.add_argument("--nprobe", default="1,8,32", help="comma-separated nprobe values of the IVF arms")
     ap.add_argument("--ivf-iters", type=int, default=10, help="k-means iterations of the index build")
@@ -145,6 +153,11 @@ def main():
         seen = (ops.sort_exclusions(torch.randint(0, a.N, (a.M * a.seen,), device=dev, generator=g), offs, a.N), offs)
         arms["filtered_noop"] = lambda: ops.topk_mips(q, c, a.k, splits=a.splits, allow=ones, exclude=empty)
         arms["filtered"] = lambda: ops.topk_mips(q, c, a.k, splits=a.splits, allow=mask, exclude=seen)
+    rank_ts = [int(x) for x in a.ranks.split(",")] if a.ranks else []
+    for T in rank_ts:
+        tv = torch.randint(0, a.N, (a.M * T,), device=dev, generator=g).to(torch.int32)
+        to = torch.arange(a.M + 1, dtype=torch.int64, device=dev) * T
+        arms[f"ranks_t{T}"] = lambda tv=tv, to=to: ops.target_ranks(q, c, tv, to, splits=a.splits)
     nprobes = [int(x) for x in a.nprobe.split(",")] if a.ivf else []
     if a.ivf:
         from two_tower_recommender_model_amd.ivf import build_ivf_index
@@ -219,6 +232,11 @@ def main():
             res[n]["ratio_to_fused"] = round(res[n]["median_ms"] / res["fused"]["median_ms"], 4)
         res["filtered_noop"]["equals_fused"] = bool(torch.equal(outs["filtered_noop"][0], outs["fused"][0]) and
                                                     torch.equal(outs["filtered_noop"][1], outs["fused"][1]))
+    for T in rank_ts:
+        n = f"ranks_t{T}"
+        res[n]["ratio_to_fused"] = round(res[n]["median_ms"] / res["fused"]["median_ms"], 4)
+        res[n]["pairs"] = a.M * T
+        res[n]["mean_rank"] = round(float(outs[n].to(torch.float64).mean()), 1)
     if a.large:
         res["fused_large"]["ratio_to_fused"] = round(res["fused_large"]["median_ms"] / res["fused"]["median_ms"], 4)
         res["fused_large"]["equals_fused"] = bool(torch.equal(outs["fused_large"][0], outs["fused"][0]) and

@@ -334,6 +334,9 @@ SIGNATURES = {
     "tt_topk_mips_large_workspace_bytes": (_sz, [_i64, _i64, _int, _int]),
     "tt_topk_mips_large": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _sz, _vp]),
+    "tt_target_ranks_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int]),
+    "tt_target_ranks": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp,
+                               _i64, _int, _vp, _vp, _vp, _sz, _vp]),
     "tt_ivf_scan_workspace_bytes": (_sz, [_i64, _int, _int, _i64]),
     "tt_ivf_scan": (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp, _vp, _int,
                            _vp, _vp, _vp, _sz, _vp]),
@@ -407,6 +410,8 @@ COMPUTE_ENTRY_POINTS = [
 IVF_ENTRY_POINTS = ["tt_ivf_scan", "tt_ivf_segment_mean", "tt_ivf_mask_lists", "tt_ivf_scan_masked"]
 # the same for the large-k selection (csrc/topk_large.hip)
 TOPK_LARGE_ENTRY_POINTS = ["tt_topk_mips_large_workspace_bytes", "tt_topk_mips_large"]
+# and for the full-catalogue target ranks (csrc/rank.hip)
+RANK_ENTRY_POINTS = ["tt_target_ranks_workspace_bytes", "tt_target_ranks"]
 
 _lib = None
 _lock = threading.Lock()

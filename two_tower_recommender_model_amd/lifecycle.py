@@ -327,3 +327,62 @@ def evaluate_retrieval(step, user_rows: torch.Tensor, target_values: torch.Tenso
                             nprobe=nprobe)
     ids = torch.where(ids > 0, ids, torch.full_like(ids, -1))  # padding (label 0) is no id
     return retrieval_metrics(ids, target_values.to(ids.device), target_offsets.to(ids.device), k)
+
+
+# ---- full-catalogue rank evaluation ---------------------------------------------------------------
+
+
+def target_ranks(user_emb: torch.Tensor, item_emb: torch.Tensor, target_values: torch.Tensor,
+                 target_offsets: torch.Tensor, metric: str = "dot", bias: Optional[torch.Tensor] = None,
+                 allow: Optional[torch.Tensor] = None, seen_values: Optional[torch.Tensor] = None,
+                 seen_offsets: Optional[torch.Tensor] = None, query_chunk: int = 1 << 16) -> torch.Tensor:
+    """Each held-out item's exact rank in its user's order of the whole catalogue (ops.target_ranks):
+    what retrieve() would put at column ``rank`` for any k above it, without a list and without a limit
+    on k. ``target_values`` are item ids in the reference's labels (label i + 1 is row i, as
+    retrieve()'s ids), ``target_offsets`` [M + 1] from 0; ``metric``, ``bias``, ``allow``,
+    ``seen_values`` / ``seen_offsets`` and ``query_chunk`` as retrieve(). Returns ranks int64 [T],
+    0-based; -1 for a label outside 1..N, an item that ``allow`` denies, or one the user has seen."""
+    if metric not in ("dot", "l2"):
+        raise ValueError("metric must be 'dot' or 'l2'")
+    if metric == "l2" and bias is None:
+        bias = l2_bias(item_emb)
+    if metric == "dot":
+        bias = None
+    M, N, dev = user_emb.shape[0], item_emb.shape[0], user_emb.device
+    if target_offsets.numel() != M + 1:
+        raise ValueError("target_offsets must have M + 1 entries")
+    allow, seen = _retrieval_filters(N, M, dev, allow, seen_values, seen_offsets)
+    # label -> row; a label outside 1..N becomes row -1, which no item has
+    rows = target_values.to(device=dev, dtype=torch.int64) - 1
+    rows = torch.where((rows >= 0) & (rows < N), rows, torch.full_like(rows, -1)).to(torch.int32).contiguous()
+    offsets = target_offsets.to(device=dev, dtype=torch.int64).contiguous()
+    ranks = torch.full((rows.numel(),), -1, dtype=torch.int64, device=dev)
+    for lo in range(0, M, query_chunk):
+        n = min(query_chunk, M - lo)
+        exclude = None if seen is None else (seen[0], seen[1][lo:lo + n + 1])
+        ops.target_ranks(user_emb[lo:lo + n], item_emb, rows, offsets[lo:lo + n + 1], bias=bias, allow=allow,
+                         exclude=exclude, out=(ranks, None))
+    return ranks
+
+
+def evaluate_ranks(step, user_rows: torch.Tensor, target_values: torch.Tensor, target_offsets: torch.Tensor,
+                   ks: Sequence[int] = (1, 10, 100, 1000), metric: str = "dot", item_emb: Optional[torch.Tensor] = None,
+                   allow: Optional[torch.Tensor] = None, seen_values: Optional[torch.Tensor] = None,
+                   seen_offsets: Optional[torch.Tensor] = None, query_chunk: int = 1 << 16) -> Dict[str, object]:
+    """evaluate_retrieval() under the full-ranking protocol: every held-out item's exact rank among the
+    items its user may be shown (target_ranks above; the query tower as retrieve_fused runs it, the
+    item tower by export_fused unless ``item_emb`` is passed), then metrics.rank_metrics' dict:
+    recall@k and nDCG@k for every k of ``ks`` from the one pass — equal to evaluate_retrieval's at
+    each k —, MRR, the mean and median rank. No k limit and no top-k selection. The exact order only:
+    ranks under an IVF index are not defined here."""
+    from .metrics import rank_metrics
+
+    towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
+    x = step.tables.table_view(0)[user_rows.to(step.device)]
+    for w, b in towers[0]:
+        x = ops.linear_fwd([x], [w.contiguous()], [b], relu=True)[0]
+    if item_emb is None:
+        item_emb = export_fused(step, "candidate")[1]
+    ranks = target_ranks(x, item_emb, target_values, target_offsets, metric=metric, allow=allow, seen_values=seen_values,
+                         seen_offsets=seen_offsets, query_chunk=query_chunk)
+    return rank_metrics(ranks, target_offsets.to(ranks.device), ks)

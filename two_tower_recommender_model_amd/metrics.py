@@ -1,5 +1,6 @@
 """Evaluation metrics on device: binary AUROC (below) and the retrieval metrics of
-04_evaluate_retrieval.py (``retrieval_metrics``, at the end).
+04_evaluate_retrieval.py (``retrieval_metrics`` from top-k lists and ``rank_metrics`` from exact target
+ranks, at the end).
 
 Binary AUROC — the metric the reference's evaluate() computes with
 ``torchmetrics.AUROC(task="binary")`` (03_model_training.py:524, :545-551; torchmetrics is not part
@@ -166,3 +167,68 @@ def retrieval_metrics(pred_ids: torch.Tensor, target_values: torch.Tensor, targe
     return {"recall_at_k": mean(recall), "precision_at_k": mean(precision), "ndcg_at_k": mean(ndcg),
             "per_query": {"recall_at_k": recall, "precision_at_k": precision, "ndcg_at_k": ndcg},
             "queries": n, "empty_queries": M - n, "k": k}
+
+
+def rank_metrics(ranks: torch.Tensor, target_offsets: torch.Tensor, ks=(1, 10, 100, 1000)):
+    """The retrieval metrics for every k at once from the targets' exact ranks (ops.target_ranks: the
+    full-ranking protocol): ``ranks`` [T] int64, 0-based, -1 for an ineligible target; query m's
+    targets are positions ``target_offsets[m]:target_offsets[m + 1]`` (the offsets may start past 0).
+    Per k, "recall_at_k" and "ndcg_at_k" are retrieval_metrics' of the top-k lists that hold exactly
+    the targets of rank < k at their ranks: a hit is 0 <= rank < k, gain 1, discount log2(rank + 2),
+    IDCG over min(|relevant|, k) ranks; an ineligible target stays in |relevant| (it can never be
+    retrieved); queries without targets are left out of the means (counted in "empty_queries",
+    per-query values nan). precision@k is not reported: its denominator is the number of ids a list
+    holds, min(k, the query's eligible items), which the ranks do not carry.
+    Returns {"ks", "recall_at_k": {k: mean}, "ndcg_at_k": {k: mean}, "mrr" (mean over the non-empty
+    queries of 1 / (1 + the best eligible rank), 0 where none is eligible), "mean_rank",
+    "median_rank" (over the eligible targets; nan when there is none), "ineligible_targets",
+    "queries", "empty_queries", "per_query": {"recall_at_k": {k: [M] float64}, "ndcg_at_k": {k: [M]
+    float64}, "reciprocal_rank": [M] float64}}. Plain torch, any device."""
+    dev = ranks.device
+    r = ranks.to(torch.int64)
+    offs = target_offsets.to(torch.int64).to(dev)
+    M = offs.numel() - 1
+    nrel = offs[1:] - offs[:-1]
+    lo, hi = int(offs[0]), int(offs[-1])
+    r = r[lo:hi]
+    owner = torch.repeat_interleave(torch.arange(M, device=dev), nrel)
+    ok = r >= 0
+    nonempty = nrel > 0
+    n = int(nonempty.sum())
+    nan = torch.full((M,), float("nan"), dtype=torch.float64, device=dev)
+
+    def mean(x):
+        return float(x[nonempty].sum() / n) if n else float("nan")
+
+    kmax = max(ks) if len(ks) else 0
+    cum = torch.cat([torch.zeros(1, dtype=torch.float64, device=dev),
+                     torch.cumsum(1.0 / torch.log2(torch.arange(2, kmax + 2, dtype=torch.float64, device=dev)), 0)])
+    disc = 1.0 / torch.log2(r.clamp(min=0).to(torch.float64) + 2.0)
+    out = {"ks": tuple(ks), "recall_at_k": {}, "ndcg_at_k": {}, "per_query": {"recall_at_k": {}, "ndcg_at_k": {}}}
+    for k in ks:
+        hit = ok & (r < k)
+        hits = torch.zeros(M, dtype=torch.float64, device=dev).index_add_(0, owner, hit.to(torch.float64))
+        gain = torch.where(hit, disc, torch.zeros_like(disc))
+        dcg = torch.zeros(M, dtype=torch.float64, device=dev).index_add_(0, owner, gain)
+        idcg = cum[nrel.clamp(max=k)]
+        recall = torch.where(nonempty, hits / nrel.clamp(min=1).to(torch.float64), nan)
+        ndcg = torch.where(nonempty, dcg / idcg.clamp(min=1e-300), nan)
+        out["recall_at_k"][k] = mean(recall)
+        out["ndcg_at_k"][k] = mean(ndcg)
+        out["per_query"]["recall_at_k"][k] = recall
+        out["per_query"]["ndcg_at_k"][k] = ndcg
+    big = torch.iinfo(torch.int64).max
+    best = torch.full((M,), big, dtype=torch.int64, device=dev)
+    if r.numel():
+        best.scatter_reduce_(0, owner, torch.where(ok, r, torch.full_like(r, big)), reduce="amin")
+    rr = torch.where(best < big, 1.0 / (best.clamp(max=big - 1).to(torch.float64) + 1.0), torch.zeros_like(nan))
+    rr = torch.where(nonempty, rr, nan)
+    elig = r[ok].to(torch.float64)
+    out["per_query"]["reciprocal_rank"] = rr
+    out["mrr"] = mean(rr)
+    out["mean_rank"] = float(elig.mean()) if elig.numel() else float("nan")
+    out["median_rank"] = float(elig.median()) if elig.numel() else float("nan")
+    out["ineligible_targets"] = int((~ok).sum())
+    out["queries"] = n
+    out["empty_queries"] = M - n
+    return out

@@ -994,6 +994,53 @@ def topk_mips_large_workspace_bytes(M: int, N: int, k: int, splits: Optional[int
     return int(_lib_().tt_topk_mips_large_workspace_bytes(M, N, k, 0 if splits is None else int(splits)))
 
 
+def target_ranks(queries: torch.Tensor, items: torch.Tensor, target_values: torch.Tensor, target_offsets: torch.Tensor,
+                 bias: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
+                 exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, splits: Optional[int] = None,
+                 return_scores: bool = False, out: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None):
+    """Each target's exact rank in its query's order of the whole catalogue (tt_target_ranks), without
+    a top-k list and so without a limit on k: for query m and each item row index t in
+    ``target_values[target_offsets[m]:target_offsets[m + 1]]`` (int32 [T]; int64 offsets [M + 1],
+    absolute, any start: a chunk of queries takes a view of the offsets), the number of items eligible
+    for m that precede t under topk_mips' total order (higher score first, equal scores by lower
+    index), 0-based. Operands, ``bias``, ``allow``, ``exclude`` and ``splits`` as topk_mips. Returns
+    ranks int64 [T] (with ``return_scores`` also the targets' scores fp32 [T]), indexed like
+    ``target_values``: rank j exactly when column j of topk_mips(..., k > j) holds t, the score that
+    column's bits; -1 / -inf for a target outside [0, N), denied by ``allow`` or in m's own exclusion
+    segment. Positions outside [target_offsets[0], target_offsets[M]) are not written: they hold -1 /
+    -inf, or what ``out`` = (ranks, scores or None) held, the tensors that calls over chunks of the
+    queries fill between them. Bit-identical across runs, ``splits`` and query chunkings; no host sync
+    (the workspace is sized by target_values.numel() and exclude[0].numel())."""
+    M, N, E, dev, S, _, _, xv, xo = _topk_operands("target_ranks", queries, items, 0, bias, splits, allow, exclude)
+    _dev(target_values, target_offsets)
+    if target_values.dtype != torch.int32 or target_values.dim() != 1 or not target_values.is_contiguous():
+        raise _lib.TTError("target_ranks: target_values must be contiguous int32 [T]")
+    if target_offsets.dtype != torch.int64 or target_offsets.dim() != 1 or target_offsets.numel() != M + 1 or \
+            not target_offsets.is_contiguous():
+        raise _lib.TTError("target_ranks: target_offsets must be contiguous int64 [M + 1]")
+    T = target_values.numel()
+    L = 0 if xv is None else xv.numel()
+    if out is not None:
+        ranks, scores = out
+        _dev(ranks, scores)
+        if ranks.dtype != torch.int64 or ranks.shape != (T,) or not ranks.is_contiguous() or \
+                (scores is not None and (scores.dtype != torch.float32 or scores.shape != (T,) or
+                                         not scores.is_contiguous())):
+            raise _lib.TTError("target_ranks: out must be (int64 [T], fp32 [T] or None), contiguous")
+        if return_scores and scores is None:
+            raise _lib.TTError("target_ranks: return_scores needs out's scores")
+    else:
+        ranks = torch.full((T,), -1, dtype=torch.int64, device=dev)
+        scores = torch.full((T,), float("-inf"), dtype=torch.float32, device=dev) if return_scores else None
+    lib = _lib_()
+    ws = scratch(lib.tt_target_ranks_workspace_bytes(M, N, T, L, S), dev, "target_ranks")
+    check(lib.tt_target_ranks(ptr(queries), _x_code(queries), queries.stride(0), ptr(items), _x_code(items),
+                              items.stride(0), ptr(bias), M, N, E, ptr(target_values), ptr(target_offsets), T,
+                              ptr(allow), ptr(xv), ptr(xo), L, S, ptr(ranks), ptr(scores), ptr(ws), ws.numel(),
+                              stream_handle(dev)), "target_ranks")
+    return (ranks, scores) if return_scores else ranks
+
+
 def ivf_scan(queries: torch.Tensor, rows: torch.Tensor, labels: torch.Tensor, list_begin: torch.Tensor,
              list_len: torch.Tensor, probes: torch.Tensor, k: int, bias: Optional[torch.Tensor] = None,
              exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
