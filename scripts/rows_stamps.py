@@ -2,7 +2,8 @@
 library) inside the production ring at the north-star shape: for each point, the median over
 workgroups of each wave's stamp (us from the workgroup's first wave start). Points: 0 start, 1 loads
 issued, 2 loads landed, 3 past barrier 1, 4 layer 0, 5 layer 1 (+ exchange write), 6 X / h strips,
-7 past barrier 2, 8 logit + dZ1, 9 dZ0, 10 dX, 11 row update / dX stores, 12 dZ strips, 13 bias sums,
+7 past barrier 2, 8 logit + dZ1, 9 dZ0, 10 dX, 11 row update / dX stores, 12 dZ strips, 13 bias sums
+(since the column sums run under dZ0 and dX: only the partials' scalar loads, in front of barrier 3),
 14 past barrier 3, 15 end. The image wave (wave 4) stamps its own points in slot 8: 0 start, 1 image
 DMAs issued, 2 image landed, 3 past barrier 1. TT_EXPERIMENT_LIB may name an earlier experiment build
 under lib_var/; such a library may have no image wave and then never writes slot 8 (whatever the

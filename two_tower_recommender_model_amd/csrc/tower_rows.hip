@@ -58,26 +58,34 @@ __device__ __forceinline__ bf16x8 rk_pack(const f32x4& a, const f32x4& b) {
   }
   return v;
 }
-// acc[mt] (mt < MT) = sum over k-steps s < S of A(mt, s) x b[s]: the A fragments of k-step s + 1
-// are read (into the other of two register sets) before k-step s's MFMAs issue, so with one wave
-// per SIMD each k-step's LDS latency hides behind the previous step's MFMAs
-template <int MT, int S, bool BWD>
-__device__ __forceinline__ void rk_gemm(f32x4 (&acc)[8], const char* img, const bf16x8 (&b)[4], int lane) {
+// the A fragments (M-tiles mt < MT) of k-step s of a product, issued into one register set
+template <int MT, bool BWD>
+__device__ __forceinline__ void rk_frags(bf16x8 (&f)[8], const char* img, int s, int lane) {
   const int n = lane & 15, q = lane >> 4;
-  bf16x8 fa[2][MT];
 #pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    acc[mt] = (f32x4)(0.f);
-    fa[0][mt] = BWD ? rk_abwd(img, mt, 0, lane) : rk_afwd(img, mt, 0, n, q);
-  }
+  for (int mt = 0; mt < MT; ++mt) f[mt] = BWD ? rk_abwd(img, mt, s, lane) : rk_afwd(img, mt, s, n, q);
+}
+// acc[mt] (mt < MT) = sum over k-steps s < S of A(mt, s) x b[s], as one link of the fragment
+// pipeline that runs through all the products of the chain: the product's k-step 0 is already in
+// flight in fa[0] when it starts (rk_frags, issued by the product before it), the fragments of
+// k-step s + 1 are read into the other register set before k-step s's MFMAs issue, and in front
+// of its last k-step's MFMAs the product issues the NEXT product's k-step 0 (next(set): the weight
+// fragments depend on the image only, never on an activation; S is even, so that set is fa[0]
+// again). No product starts with an LDS round trip of its own, and none waits behind the
+// epilogue of the one before. fill(s) is vector work without LDS reads that runs beside k-step
+// s's MFMAs, behind the reads' issue (the bias column sums under the LDS-bound backward products)
+template <int MT, int S, bool BWD, typename Next, typename Fill>
+__device__ __forceinline__ void rk_gemm(f32x4 (&acc)[8], bf16x8 (&fa)[2][8], const char* img, const bf16x8 (&b)[4],
+                                        int lane, Next next, Fill fill) {
+  static_assert(S % 2 == 0, "the next product's k-step 0 goes to set 0");
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) acc[mt] = (f32x4)(0.f);
 #pragma unroll
   for (int s = 0; s < S; ++s) {
-    if (s + 1 < S) {
-#pragma unroll
-      for (int mt = 0; mt < MT; ++mt)
-        fa[(s + 1) & 1][mt] = BWD ? rk_abwd(img, mt, s + 1, lane) : rk_afwd(img, mt, s + 1, n, q);
-    }
+    if (s + 1 < S) rk_frags<MT, BWD>(fa[(s + 1) & 1], img, s + 1, lane);
+    else next(fa[(s + 1) & 1]);
     __builtin_amdgcn_sched_barrier(0);
+    fill(s);
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
       acc[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[s & 1][mt], b[s], acc[mt], 0, 0, 0);
@@ -103,13 +111,15 @@ __device__ __forceinline__ void rk_halve(float* v, int n) {
     v[i] = keep + rk_xor<X>(send);
   }
 }
+// one level l of the four (lane bit 3 - l), in order: the caller spreads them over the k-steps of a
+// product
 template <int NV>
-__device__ __forceinline__ void rk_colsum(float (&v)[NV], int n) {
+__device__ __forceinline__ void rk_colsum_level(float (&v)[NV], int n, int l) {
   static_assert(NV == 32 || NV == 16, "column sum of 32 or 16 values per lane");
-  rk_halve<8, NV / 2>(v, n);
-  rk_halve<4, NV / 4>(v, n);
-  rk_halve<2, NV / 8>(v, n);
-  rk_halve<1, NV / 16>(v, n);
+  if (l == 0) rk_halve<8, NV / 2>(v, n);
+  else if (l == 1) rk_halve<4, NV / 4>(v, n);
+  else if (l == 2) rk_halve<2, NV / 8>(v, n);
+  else rk_halve<1, NV / 16>(v, n);
 }
 // row-major operand strip ([Bp][nf] bf16, what the tail's wgrad_lds_block_rm reads): lane (q, n)
 // stores its 16-B pieces (features 32 s + 8 q .. + 7) of batch row m; a wave instruction writes 16
@@ -232,7 +242,7 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   __shared__ __attribute__((aligned(16))) char wimg[RK_IMG];         // both towers' W0, W1 (rk_off)
   __shared__ __attribute__((aligned(16))) float xo[2][2][16 * 64];  // tower outputs per (tower, row half)
   __shared__ float bsum[2][RK_W0 + RK_W1];                          // row half 1's bias partials
-  __shared__ float lrow[TR];                                        // row losses
+  __shared__ __attribute__((aligned(16))) float lrow[TR];           // row losses
   __shared__ __attribute__((aligned(16))) float xr[4][16 * IN];     // per wave: its 16 gathered rows
                                                                     // (fp32, 16-B chunk c of row n at c ^ n)
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -421,9 +431,12 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   if (UPD) asm volatile("" ::"s"(in_max), "s"(grad_scale), "s"(fB), "s"(slots), "s"(xt_t), "s"(act_t), "s"(us_t));
   else asm volatile("" ::"s"(in_max), "s"(grad_scale), "s"(fB), "s"(xt_t), "s"(act_t));
   RK_STAMP(2);
-  __syncthreads();  // barrier 1: the image wave's DMAs landed before it arrived
-  RK_STAMP(3);
-  // this lane's row in the B layout: xv[mt] = features 32 (mt >> 1) + 8 q + 4 (mt & 1) .. + 3 (fp32)
+  // this lane's row in the B layout: xv[mt] = features 32 (mt >> 1) + 8 q + 4 (mt & 1) .. + 3 (fp32).
+  // In front of barrier 1: only this wave reads these rows, and its own vmcnt(0) above is all the
+  // ordering an LDS-DMA asks of its issuing wave, so the LDS round trip and the converts run inside
+  // the wait for the image instead of at the head of the chain. (Not the X strip's stores: in front
+  // of the barrier they share the vector memory path with the image wave's DMAs and held the image
+  // back 0.4-0.56 us, profiles/r11_t1_chain_stamps.log)
   f32x4 xv[8];
   bf16x8 xb[4];
   if (IDX) {  // the bf16 B operand straight from the returned rows
@@ -442,6 +455,29 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     }
 #pragma unroll
     for (int s2 = 0; s2 < NI; ++s2) xb[s2] = rk_pack(xv[2 * s2], xv[2 * s2 + 1]);
+  }
+  // (the strip row's address in vector registers from here: its scalars end in front of the
+  // barrier; typed as a global pointer, since one that went through the pin as a generic pointer
+  // is stored through with flat instructions, which turn every counted LDS wait into a full one)
+  typedef __attribute__((address_space(1))) bf16x8 glb_bf16x8;
+  glb_bf16x8* xrow = (glb_bf16x8*)(xt_t + m * in_max);
+  asm volatile("" : "+v"(xrow));
+  __builtin_amdgcn_sched_barrier(0);
+  __syncthreads();  // barrier 1: the image wave's DMAs landed before it arrived
+  RK_STAMP(3);
+  // ---- the fragment pipeline starts: layer 0's k-step 0, the first thing issued behind barrier 1
+  // and never in front of it (the LDS still holds the previous launch's image there: the previous
+  // step's weights, stale by one Adam step, returned without a stall)
+  const char* img0 = wimg + t * RK_IMG_T;
+  const char* img1 = img0 + RK_W0 * 256;
+  bf16x8 fa[2][8];
+  rk_frags<8, false>(fa[0], img0, 0, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  // the T1 -> T2 strip of X (row-major), fire-and-forget: issued before the layer's MFMAs so the
+  // stores drain under them (likewise h's after layer 0, the dZ strips before dX)
+  if (!TDBG(512)) {  // (TDBG: timing only)
+#pragma unroll
+    for (int s = 0; s < NI; ++s) xrow[4 * s + q] = xb[s];  // rk_strip's stores
   }
   // UPD, past barrier 1 (nothing waits on these until the row update; the claim landed with the id,
   // so neither waits for a round trip here): the slot word (its low half holds the lookup count:
@@ -462,14 +498,10 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     s_old = us_t[r >= 0 ? r : 0];
   }
   __builtin_amdgcn_sched_barrier(0);
-  const char* img0 = wimg + t * RK_IMG_T;
-  const char* img1 = img0 + RK_W0 * 256;
-  // ---- 1. layer 0: h^T = relu(W0 X^T + b0), 8 M-tiles x 4 k-steps
+  auto no_fill = [](int) {};
+  // ---- 1. layer 0: h^T = relu(W0 X^T + b0), 8 M-tiles x 4 k-steps (then W1's k-step 0)
   f32x4 acc[8];
-  // the T1 -> T2 strip of X (row-major), fire-and-forget: issued before the layer's MFMAs so the
-  // stores drain under them (likewise h's after layer 0, the dZ strips before dX)
-  if (!TDBG(512)) rk_strip<NI>(xb, xt_t + m * in_max, q);  // (TDBG: timing only)
-  rk_gemm<8, NI, false>(acc, img0, xb, lane);
+  rk_gemm<8, NI, false>(acc, fa, img0, xb, lane, [&](bf16x8(&f)[8]) { rk_frags<4, false>(f, img1, 0, lane); }, no_fill);
   RK_STAMP(4);
   bf16x8 hb[4];
 #pragma unroll
@@ -484,8 +516,33 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   }
   if (!TDBG(256)) rk_strip<4>(hb, act_t + m * MAXW, q);
   // ---- 2. layer 1: out^T = relu(W1 h^T + b1) (fp32), 4 M-tiles x 4 k-steps; exchanged in LDS
+  // (then dZ0's k-step 0, W1^T: the exchange, barrier 2, the logit, the BCE and dZ1 run under it)
   f32x4 uo[4];
-  rk_gemm<4, 4, false>(acc, img1, hb, lane);
+  rk_gemm<4, 4, false>(acc, fa, img1, hb, lane, [&](bf16x8(&f)[8]) { rk_frags<8, true>(f, img1, 0, lane); }, no_fill);
+  // ---- the update batch (the rest of the tower's line 1, the table rows, RkCommon line 1): issued
+  // here, so that barrier 2's full LDS wait, which the exchange pays anyway, covers their round
+  // trip. Scalar loads return out of order: one in flight turns every counted LDS wait of a product
+  // into a full one, so none is outstanding between barrier 2 and the end of dX (the pin behind the
+  // barrier keeps the loads here instead of at their uses, the list's inside its branch). The
+  // gradient rows and the logits come with it, except with UPD, which has no scalar register to
+  // spare across the backward products and fetches them under the write-back's one LDS wait; the
+  // bias and loss partials' bases come under barrier 3's wait in every form
+  __bf16* const dzt0_t = T.dzt0;
+  __bf16* const dzt1_t = T.dzt1;
+  float* const uw_t = T.uw;
+  const float ulr = C.ulr, ueps = C.ueps;
+  const int nseg = C.nseg;
+  float* grow_t = nullptr;
+  float* prow_t = nullptr;
+  int64_t ldp = 0;
+  float* logits = nullptr;
+  if constexpr (!UPD) {
+    grow_t = T.grow;
+    prow_t = T.prow;
+    ldp = C.ldp;
+    logits = C.logits;
+  }
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int mt = 0; mt < 4; ++mt) uo[mt] = acc[mt];
 #pragma unroll
@@ -498,6 +555,8 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   RK_STAMP(5);
   RK_STAMP(6);
   __syncthreads();
+  if (UPD) asm volatile("" ::"s"(dzt0_t), "s"(dzt1_t), "s"(uw_t), "s"(ulr), "s"(ueps), "s"(nseg));
+  else asm volatile("" ::"s"(dzt0_t), "s"(dzt1_t), "s"(grow_t), "s"(prow_t), "s"(ldp), "s"(logits));
   RK_STAMP(7);
   // ---- 3. logit (both towers compute it: the same products in the same order), BCE, dlogit
   f32x4 vo[4];
@@ -533,10 +592,17 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     const float rc = __builtin_amdgcn_rcpf(1.f + e);
     dl = ((x >= 0.f ? rc : e * rc) - y) * (grad_scale / fB);
   }
-  // (the row half per lane from here on: the wave-uniform copy would hold a scalar register from
-  // the entry to the end)
-  const int hv = (int)(threadIdx.x >> 6) & 1;
-  if (t == 0 && q == 0) lrow[16 * hv + n] = lo;
+  // (the row half, the tower and the lane per lane from here on, each from a thread index the
+  // compiler cannot share between its uses: the wave-uniform copies and the lane masks shared with
+  // the prologue would hold scalar registers from the entry to the end, and the chain has none to
+  // spare. Tower 0's lanes q == 0: thread index bits 7, 5 and 4 clear)
+  auto tid = [] {
+    uint32_t v = threadIdx.x;
+    asm volatile("" : "+v"(v));
+    return v;
+  };
+  const int hv = (int)(tid() >> 6) & 1;
+  if ((tid() & 0xB0u) == 0u) lrow[16 * hv + n] = lo;
   // ---- 4. dZ1 = dlogit * other * (self > 0) (fp32: bias sums; bf16: the next product, the strip)
   float z1[16];
   bf16x8 z1b[4];
@@ -553,18 +619,14 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   }
   // ---- 5. dZ0^T = (W1^T dZ1^T) * (h > 0): 8 M-tiles x 2 k-steps
   RK_STAMP(8);
-  // ---- the update batch (the rest of the tower's line 1, the table rows, RkCommon line 1), issued
-  // in front of this product, whose LDS waits cover their round trip (the pin behind the product
-  // keeps the loads here instead of at their uses, the list's inside its branch)
-  __bf16* const dzt0_t = T.dzt0;
-  __bf16* const dzt1_t = T.dzt1;
-  float* const uw_t = T.uw;
-  const float ulr = C.ulr, ueps = C.ueps;
-  int32_t* const multi = C.multi;
-  const int nseg = C.nseg;
-  rk_gemm<8, 2, true>(acc, img1, z1b, lane);
-  if (UPD) asm volatile("" ::"s"(dzt0_t), "s"(dzt1_t), "s"(uw_t), "s"(ulr), "s"(ueps), "s"(multi), "s"(nseg));
-  else asm volatile("" ::"s"(dzt0_t), "s"(dzt1_t));
+  // (then dX's k-step 0, W0^T). The backward products are LDS-bound and leave the vector ALU idle:
+  // db1's column sums over the wave's rows (two of rk_colsum's four levels per k-step) run beside
+  // this product's MFMAs, db0's beside dX's, each long before the barrier that combines them
+  rk_gemm<8, 2, true>(acc, fa, img1, z1b, lane, [&](bf16x8(&f)[8]) { rk_frags<MTI, true>(f, img0, 0, lane); },
+                      [&](int s) {
+                        rk_colsum_level<16>(z1, n, 2 * s);
+                        rk_colsum_level<16>(z1, n, 2 * s + 1);  // lane n: k = n
+                      });
   float z0[32];
   bf16x8 z0b[4];
 #pragma unroll
@@ -585,27 +647,17 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
   if (!TDBG(128)) rk_strip<4>(z0b, dzt0_t + m * MAXW, q);
   // ---- 6. dX^T = W0^T dZ0^T: 8 M-tiles x 4 k-steps; acc[mt] = dX features of xv[mt]
   RK_STAMP(9);
-  // ---- the gradient rows and the epilogue's pointers (lines the update batch brought into the
-  // scalar cache): in front of the dX product; UPD, which has no register to spare across it,
-  // fetches them under the write-back's one LDS wait, in front of the row stores
-  float* grow_t = nullptr;
-  float* prow_t = nullptr;
-  int64_t ldp = 0;
-  float* db0_t = nullptr;
-  float* db1_t = nullptr;
-  float* logits = nullptr;
-  float* loss_part = nullptr;
-  if constexpr (!UPD) {
-    grow_t = T.grow;
-    prow_t = T.prow;
-    ldp = C.ldp;
-    db0_t = T.db0;
-    db1_t = T.db1;
-    logits = C.logits;
-    loss_part = C.loss_part;
+  // (the last product: nothing to prefetch; one level of db0's column sums per k-step)
+  rk_gemm<MTI, 4, true>(acc, fa, img0, z0b, lane, [](bf16x8(&)[8]) {},
+                        [&](int s) { rk_colsum_level<32>(z0, n, s); });  // lane n: k = 2 n + i, i < 2 (k = 4 mt + j)
+  // row half 1's bias partials at once (a dead wave's are exact zeros: every z of a dead row is 0.f);
+  // feature of value k = 4 mt + j: 32 (mt >> 1) + 8 q + 4 (mt & 1) + j
+  auto feat = [&](int k) { return 32 * ((k >> 2) >> 1) + 8 * q + 4 * ((k >> 2) & 1) + (k & 3); };
+  if (hv == 1) {
+    bsum[t][feat(2 * n)] = z0[0];
+    bsum[t][feat(2 * n + 1)] = z0[1];
+    bsum[t][RK_W0 + feat(n)] = z1[0];
   }
-  rk_gemm<MTI, 4, true>(acc, img0, z0b, lane);
-  if constexpr (!UPD) asm volatile("" ::"s"(grow_t), "s"(prow_t), "s"(ldp), "s"(db0_t), "s"(db1_t), "s"(logits), "s"(loss_part));
   RK_STAMP(10);
   // ---- 7. the row: UPD + looked up once -> row-wise Adagrad in place (the K3 update's arithmetic and
   // summation tree: feature groups of 4 combined at group bits 4, 3 (in lane), 2, 1 (lanes ^ 32,
@@ -621,6 +673,10 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     store_dx = live;
   }
   if (UPD) {
+    // (the list's base from the line nseg brought into the scalar cache: past the products, under
+    // the wait of the shuffles below)
+    int32_t* const multi = C.multi;
+    __builtin_amdgcn_sched_barrier(0);
     float e2[2];
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
@@ -637,10 +693,12 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
       c2 += __shfl_xor(c2, 16, 64);
       e2[hh] = c2;
     }
+    asm volatile("" ::"s"(multi));
     RK_STAMP2(0);
     const float sq = e2[0] + e2[1];
     const float snew = rw_state(s_old, sq, IN);
     const float step = rw_step(snew, ulr, ueps);
+    float* us_w;
     const uint32_t cnt = word & (uint32_t)DD_CNT_MASK;
     const bool single = r >= 0 && cl >= 0 && cnt == 1u;
     {
@@ -664,7 +722,8 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     RK_STAMP2(1);
     asm volatile("" ::: "memory");  // LDS is in order per wave: only the compiler must not reorder
     {
-      const int rr0 = lane / CPR, pc = lane % CPR;
+      const int wl = (int)(tid() & 63u);
+      const int rr0 = wl / CPR, pc = wl % CPR;
       float* wtab = uw_t;
       // as a batch: every shuffle (the row's index where it is updated here, -1 elsewhere: one
       // value carries the index and the predicate), every LDS read, one wait; then the stores under
@@ -675,17 +734,19 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
       grow_t = T.grow;
       prow_t = T.prow;
       ldp = C.ldp;
-      db0_t = T.db0;
-      db1_t = T.db1;
       logits = C.logits;
-      loss_part = C.loss_part;
+      // the state's base again, through a tower index the compiler cannot match with the entry's:
+      // held from the late batch to here it costs the chain the scalar pair it does not have
+      int tw = t;
+      asm volatile("" : "+s"(tw));
+      us_w = const_cast<float*>(a.rk.tw[tw].us);
 #pragma unroll
       for (int i = 0; i < NDMA; ++i) rid[i] = __shfl((long long)rsend, RPI * i + rr0, 64);
 #pragma unroll
       for (int i = 0; i < NDMA; ++i) w[i] = *reinterpret_cast<const f32x4*>(xw + (RPI * i + rr0) * IN + 4 * pc);
       rk_pin<NDMA>(rid);
       rk_pin<NDMA>(w);
-      asm volatile("" ::"s"(grow_t), "s"(prow_t), "s"(ldp), "s"(db0_t), "s"(db1_t), "s"(logits), "s"(loss_part));
+      asm volatile("" ::"s"(grow_t), "s"(prow_t), "s"(ldp), "s"(logits), "s"(us_w));
 #pragma unroll
       for (int i = 0; i < NDMA; ++i) {
         const int row = RPI * i + rr0;
@@ -695,7 +756,7 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     RK_STAMP2(2);
     if (single) {
       if (q == 0) {
-        const_cast<float*>(us_t)[r] = snew;
+        us_w[r] = snew;
         slots[cl].word = DD_EMPTY;  // free: nothing else of the step reads a single slot
       }
       store_dx = prow_t != nullptr;  // dX only for inspection
@@ -708,27 +769,23 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
       *reinterpret_cast<f32x4*>(grow + 32 * (mt >> 1) + 8 * q + 4 * (mt & 1)) = acc[mt];
   }
   RK_STAMP2(3);
-  if (t == 0 && q == 0 && live) logits[m] = d;  // after the row update (see rk_strip)
+  if ((tid() & 0xB0u) == 0u && live) logits[m] = d;  // after the row update (see rk_strip)
   if (!IDX && !POOL && prow_t && live) {
     float* prow = prow_t + m * ldp;
 #pragma unroll
     for (int mt = 0; mt < MTI; ++mt) *reinterpret_cast<f32x4*>(prow + 32 * (mt >> 1) + 8 * q + 4 * (mt & 1)) = xv[mt];
   }
   RK_STAMP(11);
-  // ---- 8. bias partials (fp32 column sums over the wave's rows, then row half 0 +
+  // ---- 8. bias partials (the wave's column sums from under the backward products: row half 0 +
   // row half 1); the loss partial (the tile's 32 row losses in order)
   RK_STAMP(12);
-  rk_colsum<32>(z0, n);  // lane n: k = 2 n + i, i < 2 (k = 4 mt + j)
-  rk_colsum<16>(z1, n);  // lane n: k = n
-  // feature of value k = 4 mt + j: 32 (mt >> 1) + 8 q + 4 (mt & 1) + j
-  auto feat = [&](int k) { return 32 * ((k >> 2) >> 1) + 8 * q + 4 * ((k >> 2) & 1) + (k & 3); };
-  if (hv == 1) {
-    bsum[t][feat(2 * n)] = z0[0];
-    bsum[t][feat(2 * n + 1)] = z0[1];
-    bsum[t][RK_W0 + feat(n)] = z1[0];
-  }
+  float* const db0_t = T.db0;
+  float* const db1_t = T.db1;
+  float* const loss_part = C.loss_part;
+  __builtin_amdgcn_sched_barrier(0);
   RK_STAMP(13);
   __syncthreads();
+  asm volatile("" ::"s"(db0_t), "s"(db1_t), "s"(loss_part));
   RK_STAMP(14);
   if (hv == 0) {
     float* db0 = db0_t + (int64_t)tile * MAXW;  // by tile: T2 sums them in tile order
@@ -736,9 +793,15 @@ __device__ __forceinline__ void tower_rows_body(const TowerArgs& a) {
     db0[feat(2 * n)] = z0[0] + bsum[t][feat(2 * n)];
     db0[feat(2 * n + 1)] = z0[1] + bsum[t][feat(2 * n + 1)];
     db1[feat(n)] = z1[0] + bsum[t][RK_W0 + feat(n)];
-    if (t == 0 && lane == 0) {
+    if (tid() == 0u) {
+      // the 32 row losses as one batch of reads and one wait, then the adds in the order i = 0 .. 31
+      f32x4 lv[TR / 4];
+#pragma unroll
+      for (int i = 0; i < TR / 4; ++i) lv[i] = reinterpret_cast<const f32x4*>(lrow)[i];
+      rk_pin<TR / 4>(lv);
       float p = 0.f;
-      for (int i = 0; i < TR; ++i) p += lrow[i];
+#pragma unroll
+      for (int i = 0; i < TR; ++i) p += lv[i >> 2][i & 3];
       loss_part[tile] = p;
     }
   }
