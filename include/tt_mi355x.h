@@ -47,6 +47,8 @@
  *   tt_topk_mips_large         <- the same query at k in the thousands (04:91 asks for k = 5000)
  *   tt_target_ranks            <- the evaluation of those queries (04:202-226) from each held-out
  *                                 item's exact rank in the whole catalogue: every k at once, no top-k
+ *   tt_tower_embed             <- create_keyed_jagged_tensor + process_embeddings, 03:1056-1122 (table
+ *                                 rows through a whole tower in one launch, fp32 or bf16 result)
  *   tt_launch (a launch plan)  <- the same backward work with several roles in one launch: the
  *                                 weight gradients beside the embedding update / next-batch insert /
  *                                 shard route and gather ("launch plans" below)
@@ -734,6 +736,44 @@ int tt_target_ranks(const void* queries, int q_dtype, int64_t ldq, const void* i
                     const int64_t* target_offsets, int64_t T_cap, const uint32_t* allow, const int32_t* excl_values,
                     const int64_t* excl_offsets, int64_t L_cap, int splits, int64_t* ranks, float* scores /* nullable */,
                     void* workspace, size_t ws_bytes, void* stream);
+
+/* Fused tower inference (ABI 4 addition; csrc/tower_embed.hip): table rows through a whole tower MLP
+ * in one launch — the embedding export of 03_model_training.py:1056-1122 (a one-id bag is the row
+ * itself) and the query embeddings of the retrieval evaluation — with an fp32 or a bf16 result.
+ * Operands: table [num_rows][in_dim] fp32 with row stride ld; W[l] [widths[l]][in_l] fp32, row-major,
+ * contiguous (nn.Linear layout), in_0 = in_dim, in_l = widths[l - 1]; bias[l] fp32 [widths[l]] or NULL
+ * (no bias on that layer; `bias` itself may be NULL); widths, W and bias are host arrays of length L;
+ * out [M][widths[L - 1]] with row stride ldo, TT_F32 or TT_BF16.
+ * Row selection: output row m is the tower applied to table row r_m. rows == NULL: r_m = first_row + m
+ * (0 <= first_row, first_row + M <= num_rows). Otherwise r_m = rows[m] (TT_I32 or TT_I64; any order,
+ * duplicates allowed; first_row must be 0). An r_m outside [0, num_rows) never indexes the table: its
+ * input is the zero row (what an empty bag gives the tower in the reference) and it adds 1 to
+ * *bad_rows (device int32, nullable, zeroed by the caller; an integer count, so the atomic add does
+ * not touch reproducibility).
+ * CONTRACT: every layer is Linear + ReLU (torchrec MLP). The fp32 result is bit-identical to the chain
+ * of tt_linear_fwd(compute = TT_BF16, relu = 1) calls over the same rows: X and W rounded to bf16
+ * (nearest-even), v_mfma_f32_16x16x32_bf16 over K in ascending steps of 32 from a zero accumulator
+ * (activation row in the A position, weight row in the B position), + bias in fp32, fmaxf(x, 0), and
+ * the fp32 activation rounded to bf16 between layers, as the next tt_linear_fwd rounds it on load.
+ * The bf16 result is the fp32 result rounded once to nearest-even. The result of a row is
+ * independent of M, of the row's position, of the tile it lands in and of `rows` versus range
+ * addressing.
+ * Execution: one launch on `stream` (a persistent grid; each workgroup keeps the whole tower's weights
+ * as a bf16 LDS image); no workspace, no allocation, no synchronisation, no atomics other than
+ * bad_rows.
+ * Limits (TT_EINVAL otherwise, before any launch): in_dim and every width a multiple of 32 in
+ * [32, 128]; 1 <= L <= 4; M >= 0 (M == 0: TT_OK without a launch); 1 <= num_rows; ld >= in_dim,
+ * ld % 4 == 0, table 16-byte aligned; ldo >= widths[L - 1] with out and ldo such that rows are 16-byte
+ * aligned (ldo % 4 == 0 for fp32, % 8 for bf16); table, widths, W, every W[l] and out not NULL;
+ * row_dtype TT_I32 or TT_I64 when rows is given; out_dtype TT_F32 or TT_BF16; a shape
+ * tt_tower_embed_supported accepts. tt_tower_embed_supported is the single statement of which shapes
+ * run: 1 or 0, never an error; every in-range shape with L <= 3 is supported (an L == 4 shape is
+ * refused where the weight image does not fit in LDS beside a wave's row tile). */
+int tt_tower_embed_supported(int in_dim, int L, const int32_t* widths);
+int tt_tower_embed(const float* table, int64_t ld, int64_t num_rows, int in_dim, const void* rows, int row_dtype,
+                   int64_t first_row, int64_t M, int L, const int32_t* widths, const float* const* W,
+                   const float* const* bias /* nullable */, void* out, int out_dtype, int64_t ldo,
+                   int32_t* bad_rows /* nullable */, void* stream);
 
 /* IVF (inverted-file) approximate top-k (ABI 4 addition): the fine step of the approximate vector
  * index that 04_evaluate_retrieval.py:112-153 queries. The index holds the N item rows grouped into

@@ -337,6 +337,9 @@ SIGNATURES = {
     "tt_target_ranks_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64, _int]),
     "tt_target_ranks": (_int, [_vp, _int, _i64, _vp, _int, _i64, _vp, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp,
                                _i64, _int, _vp, _vp, _vp, _sz, _vp]),
+    "tt_tower_embed_supported": (_int, [_int, _int, _pi32]),
+    "tt_tower_embed": (_int, [_vp, _i64, _i64, _int, _vp, _int, _i64, _i64, _int, _pi32, _pvp, _pvp, _vp, _int, _i64, _vp,
+                              _vp]),
     "tt_ivf_scan_workspace_bytes": (_sz, [_i64, _int, _int, _i64]),
     "tt_ivf_scan": (_int, [_vp, _int, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _int, _vp, _vp, _int,
                            _vp, _vp, _vp, _sz, _vp]),
@@ -412,6 +415,8 @@ IVF_ENTRY_POINTS = ["tt_ivf_scan", "tt_ivf_segment_mean", "tt_ivf_mask_lists", "
 TOPK_LARGE_ENTRY_POINTS = ["tt_topk_mips_large_workspace_bytes", "tt_topk_mips_large"]
 # and for the full-catalogue target ranks (csrc/rank.hip)
 RANK_ENTRY_POINTS = ["tt_target_ranks_workspace_bytes", "tt_target_ranks"]
+# and for the fused tower inference (csrc/tower_embed.hip)
+EMBED_ENTRY_POINTS = ["tt_tower_embed_supported", "tt_tower_embed"]
 
 _lib = None
 _lock = threading.Lock()

@@ -28,7 +28,7 @@ LIB_EXP = PKG / "lib_exp" / "libtt_mi355x.so"
 ARCH = "gfx950"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
-SOURCES = ["api.cpp", "kjt.hip", "embedding.hip", "gemm.hip", "loss_adam.hip", "tower.hip", "tower_t1.hip", "tower_rows.hip", "tower_tail.hip", "dedup.hip", "shard.hip", "shard_kjt.hip", "peer.hip", "retrieval.hip", "ivf.hip", "topk_large.hip", "rank.hip"]
+SOURCES = ["api.cpp", "kjt.hip", "embedding.hip", "gemm.hip", "loss_adam.hip", "tower.hip", "tower_t1.hip", "tower_rows.hip", "tower_tail.hip", "dedup.hip", "shard.hip", "shard_kjt.hip", "peer.hip", "retrieval.hip", "ivf.hip", "topk_large.hip", "rank.hip", "tower_embed.hip"]
 HEADERS = [CSRC / "tt_common.h", CSRC / "dedup.h", CSRC / "shard.h", CSRC / "tower_common.h", CSRC / "topk_common.h", CSRC / "topk_scan.h", CSRC / "topk_exact.h", INCLUDE / "tt_mi355x.h"]
 
 CFLAGS = [

@@ -131,18 +131,46 @@ def evaluate_fused(step, batches: Iterable[Tuple[Sequence[torch.Tensor], torch.T
 # ---- embedding export ----------------------------------------------------------------------------
 
 
+def _fused_tower_check(table: torch.Tensor, layers, precision: str) -> None:
+    if precision != "bf16":
+        raise ValueError("fused=True runs the bf16 chain only: precision must be 'bf16'")
+    widths = [w.shape[0] for w, _ in layers]
+    if not ops.tower_embed_supported(table.shape[1], widths):
+        raise ValueError(f"fused=True: ops.tower_embed does not run a tower {table.shape[1]} -> {widths} "
+                         "(ops.tower_embed_supported)")
+
+
 def export_embeddings(table: torch.Tensor, layers: Sequence[Tuple[torch.Tensor, torch.Tensor]],
                       chunk: int = 1 << 20, precision: str = "bf16",
-                      out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+                      out: Optional[torch.Tensor] = None, fused: bool = False,
+                      out_dtype: torch.dtype = torch.float32) -> Tuple[torch.Tensor, torch.Tensor]:
     """process_embeddings (03:1089-1117) for every row of ``table`` ([N, D] fp32, device): the
     tower MLP (Linear + ReLU on every layer) on bf16 MFMA GEMMs (fp32 accumulate; "fp32" for the
     exact path), ``chunk`` rows per launch. Returns (ids = arange(N) + 1 — the reference's labels —,
-    embeddings [N, out])."""
+    embeddings [N, out]).
+
+    ``fused=True``: each chunk is one ops.tower_embed launch over its row range instead of one
+    linear_fwd per layer (no hidden activation leaves the chip; the same bits; ``precision`` must be
+    "bf16" and the tower a shape ops.tower_embed_supported accepts, else ValueError). Only then may
+    ``out_dtype`` be torch.bfloat16: the embeddings rounded once to nearest-even, which is what every
+    retrieval kernel makes of fp32 items on load."""
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("out_dtype must be torch.float32 or torch.bfloat16")
+    if out_dtype != torch.float32 and not fused:
+        raise ValueError("out_dtype=torch.bfloat16 needs fused=True (the per-layer path writes fp32)")
     N = table.shape[0]
     width = layers[-1][0].shape[0]
+    if fused:
+        _fused_tower_check(table, layers, precision)
     if out is None:
-        out = torch.empty(N, width, dtype=torch.float32, device=table.device)
+        out = torch.empty(N, width, dtype=out_dtype, device=table.device)
+    elif out.dtype != out_dtype:
+        raise ValueError("out's dtype must be out_dtype")
     for lo in range(0, N, chunk):
+        if fused:
+            n = min(chunk, N - lo)
+            ops.tower_embed(table, layers, first_row=lo, count=n, out=out[lo:lo + n])
+            continue
         x = table[lo:lo + chunk]
         for l, (w, b) in enumerate(layers):
             y = out[lo:lo + chunk] if l == len(layers) - 1 else None
@@ -154,7 +182,7 @@ def export_embeddings(table: torch.Tensor, layers: Sequence[Tuple[torch.Tensor, 
 
 def export_fused(step, tower: str = "candidate", **kw) -> Tuple[torch.Tensor, torch.Tensor]:
     """export_embeddings of a FusedTwoTowerStep's item ("candidate", table 1) or user ("query",
-    table 0) tower."""
+    table 0) tower; ``fused`` and ``out_dtype`` (and the rest) as export_embeddings."""
     t = 1 if tower == "candidate" else 0
     towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
     return export_embeddings(step.tables.table_view(t), towers[t], **kw)
@@ -286,23 +314,40 @@ def retrieve(user_emb: torch.Tensor, item_emb: torch.Tensor, k: int = 100, metri
     return ids, scores
 
 
+def _query_embeddings(step, user_rows: torch.Tensor, fused: bool) -> torch.Tensor:
+    """Rows ``user_rows`` of the user table through the query tower: a gather and one linear_fwd per
+    layer, or (``fused``) one ops.tower_embed launch over the row list."""
+    towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
+    table = step.tables.table_view(0)
+    if fused:
+        _fused_tower_check(table, towers[0], "bf16")
+        rows = user_rows.to(step.device)
+        if rows.dtype not in (torch.int32, torch.int64):
+            rows = rows.to(torch.int64)
+        return ops.tower_embed(table, towers[0], rows=rows.contiguous())
+    x = table[user_rows.to(step.device)]
+    for w, b in towers[0]:
+        x = ops.linear_fwd([x], [w.contiguous()], [b], relu=True)[0]
+    return x
+
+
 def retrieve_fused(step, user_rows: torch.Tensor, k: int = 100, metric: str = "dot",
                    item_emb: Optional[torch.Tensor] = None, allow: Optional[torch.Tensor] = None,
                    seen_values: Optional[torch.Tensor] = None, seen_offsets: Optional[torch.Tensor] = None,
                    query_chunk: int = 1 << 16, index: Optional["IVFIndex"] = None,
-                   nprobe: int = 32) -> Tuple[torch.Tensor, torch.Tensor]:
+                   nprobe: int = 32, fused: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """retrieve() for a FusedTwoTowerStep: rows ``user_rows`` (int64 row indices) of the user table
     through the query tower (as export does), against the item table through the candidate tower
     (export_fused, unless its embeddings ``item_emb`` are passed in). ``allow``, ``seen_values`` /
     ``seen_offsets``, ``query_chunk``, ``index`` and ``nprobe`` as retrieve() (with an index the
-    item tower is not run; an item mask with an index is ``index=index.restricted(allow)``)."""
+    item tower is not run; an item mask with an index is ``index=index.restricted(allow)``).
+    ``fused=True``: the query embeddings are one ops.tower_embed launch over ``user_rows`` in place of
+    the gather and the per-layer launches, and the item export, where it is computed here, is the
+    fused one; the same bits either way."""
     _check_index_k(k, index)
-    towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
-    x = step.tables.table_view(0)[user_rows.to(step.device)]
-    for w, b in towers[0]:
-        x = ops.linear_fwd([x], [w.contiguous()], [b], relu=True)[0]
+    x = _query_embeddings(step, user_rows, fused)
     if item_emb is None and index is None:
-        item_emb = export_fused(step, "candidate")[1]
+        item_emb = export_fused(step, "candidate", fused=fused)[1]
     return retrieve(x, item_emb, k=k, metric=metric, query_chunk=query_chunk, allow=allow, seen_values=seen_values,
                     seen_offsets=seen_offsets, index=index, nprobe=nprobe)
 
@@ -311,7 +356,7 @@ def evaluate_retrieval(step, user_rows: torch.Tensor, target_values: torch.Tenso
                        k: int = 100, metric: str = "dot", item_emb: Optional[torch.Tensor] = None,
                        allow: Optional[torch.Tensor] = None, seen_values: Optional[torch.Tensor] = None,
                        seen_offsets: Optional[torch.Tensor] = None, query_chunk: int = 1 << 16,
-                       index: Optional["IVFIndex"] = None, nprobe: int = 32) -> Dict[str, object]:
+                       index: Optional["IVFIndex"] = None, nprobe: int = 32, fused: bool = False) -> Dict[str, object]:
     """Retrieval evaluation of 04_evaluate_retrieval.py:202-226 (mlflow.evaluate, model_type
     "retriever"): the top ``k`` item ids of every user row against its jagged ground truth
     (``target_values`` item ids in the reference's labels, ``target_offsets`` [M + 1]);
@@ -319,12 +364,12 @@ def evaluate_retrieval(step, user_rows: torch.Tensor, target_values: torch.Tenso
     with each user's training positives as the seen set, the held-out items are ranked among the
     items the user has not seen, which is the usual protocol. ``index`` / ``nprobe`` as retrieve():
     the approximate query (ivf.IVFIndex, or its restricted(allow) view for an item mask) in place of
-    the exact one."""
+    the exact one. ``fused`` as retrieve_fused()."""
     from .metrics import retrieval_metrics
 
     ids, _ = retrieve_fused(step, user_rows, k=k, metric=metric, item_emb=item_emb, allow=allow,
                             seen_values=seen_values, seen_offsets=seen_offsets, query_chunk=query_chunk, index=index,
-                            nprobe=nprobe)
+                            nprobe=nprobe, fused=fused)
     ids = torch.where(ids > 0, ids, torch.full_like(ids, -1))  # padding (label 0) is no id
     return retrieval_metrics(ids, target_values.to(ids.device), target_offsets.to(ids.device), k)
 
@@ -368,21 +413,19 @@ def target_ranks(user_emb: torch.Tensor, item_emb: torch.Tensor, target_values: 
 def evaluate_ranks(step, user_rows: torch.Tensor, target_values: torch.Tensor, target_offsets: torch.Tensor,
                    ks: Sequence[int] = (1, 10, 100, 1000), metric: str = "dot", item_emb: Optional[torch.Tensor] = None,
                    allow: Optional[torch.Tensor] = None, seen_values: Optional[torch.Tensor] = None,
-                   seen_offsets: Optional[torch.Tensor] = None, query_chunk: int = 1 << 16) -> Dict[str, object]:
+                   seen_offsets: Optional[torch.Tensor] = None, query_chunk: int = 1 << 16,
+                   fused: bool = False) -> Dict[str, object]:
     """evaluate_retrieval() under the full-ranking protocol: every held-out item's exact rank among the
     items its user may be shown (target_ranks above; the query tower as retrieve_fused runs it, the
     item tower by export_fused unless ``item_emb`` is passed), then metrics.rank_metrics' dict:
     recall@k and nDCG@k for every k of ``ks`` from the one pass — equal to evaluate_retrieval's at
     each k —, MRR, the mean and median rank. No k limit and no top-k selection. The exact order only:
-    ranks under an IVF index are not defined here."""
+    ranks under an IVF index are not defined here. ``fused`` as retrieve_fused()."""
     from .metrics import rank_metrics
 
-    towers = _tower_views(step.params, [step.in_q, step.in_c], step.layer_sizes)
-    x = step.tables.table_view(0)[user_rows.to(step.device)]
-    for w, b in towers[0]:
-        x = ops.linear_fwd([x], [w.contiguous()], [b], relu=True)[0]
+    x = _query_embeddings(step, user_rows, fused)
     if item_emb is None:
-        item_emb = export_fused(step, "candidate")[1]
+        item_emb = export_fused(step, "candidate", fused=fused)[1]
     ranks = target_ranks(x, item_emb, target_values, target_offsets, metric=metric, allow=allow, seen_values=seen_values,
                          seen_offsets=seen_offsets, query_chunk=query_chunk)
     return rank_metrics(ranks, target_offsets.to(ranks.device), ks)

@@ -1041,6 +1041,72 @@ def target_ranks(queries: torch.Tensor, items: torch.Tensor, target_values: torc
     return (ranks, scores) if return_scores else ranks
 
 
+# ---- fused tower inference ---------------------------------------------------------------------
+
+
+def _widths_array(widths: Sequence[int]):
+    return (C.c_int32 * max(len(widths), 1))(*[int(w) for w in widths])
+
+
+def tower_embed_supported(in_dim: int, widths: Sequence[int]) -> bool:
+    """Whether tower_embed runs a tower of this shape (tt_tower_embed_supported: the library's rule,
+    not restated here)."""
+    return bool(_lib_().tt_tower_embed_supported(int(in_dim), len(widths), _widths_array(widths)))
+
+
+def tower_embed(table: torch.Tensor, layers: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]],
+                rows: Optional[torch.Tensor] = None, first_row: int = 0, count: Optional[int] = None,
+                out: Optional[torch.Tensor] = None, out_dtype: torch.dtype = torch.float32,
+                bad_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Rows of ``table`` ([N, D] fp32, row stride >= D) through the whole tower ``layers`` =
+    [(W [n, k] fp32, bias [n] fp32 or None), ...] (Linear + ReLU on every layer) in one launch
+    (tt_tower_embed). Rows ``first_row .. first_row + count`` (count: to the table's end), or the rows
+    that ``rows`` (int32 or int64 device tensor; any order, duplicates allowed) names: one outside
+    [0, N) gives the tower's value on a zero row and adds 1 to ``bad_rows`` (int32 [1], zeroed by the
+    caller). Returns ``out`` ([M, n_last], fp32 or bf16, a strided row view is fine; allocated in
+    ``out_dtype`` when None). The fp32 result is bit-identical to the linear_fwd chain at
+    precision "bf16", the bf16 result is that rounded once to nearest-even."""
+    _dev(table, rows, out, bad_rows, *[t for wb in layers for t in wb])
+    if table.dim() != 2 or table.dtype != torch.float32 or table.stride(1) != 1:
+        raise _lib.TTError("tower_embed: table must be fp32 [N, D] with unit column stride")
+    N, D = table.shape
+    if not layers:
+        raise _lib.TTError("tower_embed: no layers")
+    ws, bs, k = [], [], D
+    for w, b in layers:
+        if w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] != k:
+            raise _lib.TTError("tower_embed: W[l] must be fp32 [n_l, n_(l-1)]")
+        if b is not None and (b.dtype != torch.float32 or b.shape != (w.shape[0],) or not b.is_contiguous()):
+            raise _lib.TTError("tower_embed: bias[l] must be contiguous fp32 [n_l] or None")
+        ws.append(w.contiguous())
+        bs.append(b)
+        k = w.shape[0]
+    widths = [w.shape[0] for w in ws]
+    if rows is not None:
+        if rows.dim() != 1 or not rows.is_contiguous():
+            raise _lib.TTError("tower_embed: rows must be a contiguous 1-d int32 or int64 tensor")
+        if count is not None and count != rows.numel():
+            raise _lib.TTError("tower_embed: count does not match rows")
+        M, code = rows.numel(), id_dtype_code(rows.dtype)
+    else:
+        M, code = (N - first_row if count is None else count), TT_I64
+    if out is None:
+        if out_dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.TTError("tower_embed: out_dtype must be torch.float32 or torch.bfloat16")
+        out = torch.empty(max(M, 0), k, dtype=out_dtype, device=table.device)
+    elif out.dim() != 2 or out.shape != (M, k) or out.stride(1) != 1 or out.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.TTError("tower_embed: out must be fp32 or bf16 [M, n_last] with unit column stride")
+    if bad_rows is not None and (bad_rows.dtype != torch.int32 or bad_rows.numel() < 1):
+        raise _lib.TTError("tower_embed: bad_rows must be an int32 tensor")
+    if M == 0:  # nothing to launch (an empty tensor has no address to pass)
+        return out
+    check(_lib_().tt_tower_embed(ptr(table), table.stride(0) if N > 1 else D, N, D, ptr(rows), code, first_row, M, len(ws),
+                                 _widths_array(widths), ptr_array(ws), ptr_array(bs), ptr(out), _x_code(out),
+                                 out.stride(0) if M > 1 else k, ptr(bad_rows),
+                                 stream_handle(table.device)), "tower_embed")
+    return out
+
+
 def ivf_scan(queries: torch.Tensor, rows: torch.Tensor, labels: torch.Tensor, list_begin: torch.Tensor,
              list_len: torch.Tensor, probes: torch.Tensor, k: int, bias: Optional[torch.Tensor] = None,
              exclude: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
